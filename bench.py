@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py - the reference's headline metric on MI355X: mel-frames/s of the K=100 DDPM reverse loop.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step,
+config); nothing else runs on the device or the host.  `--full` adds every other figure of the line below (roofline, parity, CPU and
+PyTorch-eager baselines, the split-precision experiment, in-service noise, off-shapes, the configs[4] shard, the rows around the path and,
+at N > 1, the per-rank legs).  `--dump-outputs DIR` writes what the last timed step returned, as DIR/<name>.npy in float32, after the timed
+steps (the inputs are seeded: two builds run with the same arguments can be compared output for output).
 
 N > 1: one rank per GPU over RCCL.  Either the driver launches the ranks (python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE in the environment) or, with no launcher around it, `python bench.py --gpus N` starts them itself
@@ -19,7 +25,7 @@ the 100-step reverse loop (ONE persistent kernel launch, csrc/dsd_loop.hpp; fall
 per-layer launches), de-normalisation to [B,T,80] and, for N > 1, the gather to rank 0.  Inputs are resident in HBM
 before the timed region.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      for the dominant kernel (k_loop: the whole loop; or k_layer, one residual block, on the fallback path):
                 executed fp32 FLOPs per launch / launch duration measured live with HIP events on the launch stream,
                 against the 157.3 TFLOP/s
@@ -897,10 +903,17 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--full', action='store_true',
+                    help='headline path: after the timed steps also measure and check everything else the line can carry (roofline, parity, CPU and '
+                         'PyTorch-eager baselines, `secondary`, `inservice_noise`, `offshape`, `cfg5_shard_n1`, `rows`; at N > 1 the per-rank legs); '
+                         'off: the line holds the timed steps alone')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='headline path: write the de-normalised mel of the last timed step to DIR/mel.npy (float32; at configs[4] a fixed, seeded '
+                         'sample of its utterances)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the labelled split-precision line (`secondary`) of the N = 1 run (~45 s, mostly its fp64 oracle)')
-    ap.add_argument('--no-cfg5-shard', action='store_true', help='skip the configs[4] shard leg of the N = 1 line (~5 s)')
-    ap.add_argument('--no-extras', action='store_true', help='skip `rows` / `offshape` / `inservice_noise` of the N = 1 line (~6 s)')
+    ap.add_argument('--no-secondary', action='store_true', help='skip the labelled split-precision line (`secondary`) of the --full N = 1 run (~45 s, mostly its fp64 oracle)')
+    ap.add_argument('--no-cfg5-shard', action='store_true', help='skip the configs[4] shard leg of the --full N = 1 line (~5 s)')
+    ap.add_argument('--no-extras', action='store_true', help='skip `rows` / `offshape` / `inservice_noise` of the --full N = 1 line (~6 s)')
     ap.add_argument('--tile', type=int, default=0, help='frames per workgroup of the layer kernel (0 auto, 32, 64)')
     ap.add_argument('--row', choices=['path', 'vocoder', 'train', 'fs2'], default='path',
                     help='path: the headline hot path (default); vocoder: SURVEY 8 row f2; train: row f3 (denoiser p_losses forward + backward); '
@@ -918,6 +931,10 @@ def main():
     ap.add_argument('--split', action='store_true', help='EXPERIMENT: residual layers as six bf16 plane products per fp32 product (fp32-class accuracy) '
                                                           'on the bf16 matrix pipe; per-layer kernel path; the JSON line says so in dtype / config')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.row != 'path':
+        ap.error('--dump-outputs writes the headline path\'s outputs: it cannot be combined with --row')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         return self_launch(args)
     if args.row == 'vocoder':
@@ -1015,6 +1032,20 @@ def _time_steps(step, args, world, device, dist):
     return float(elt.item()), out
 
 
+DUMP_MAX_BYTES, DUMP_SAMPLE_UTTS = 64 * 2 ** 20, 48
+
+
+def dump_outputs(dirname: str, mel) -> None:
+    """--dump-outputs: the de-normalised mel [B, T, 80] the last timed step returned, as DIR/mel.npy in float32.  A mel above 64 MB (configs[4]:
+    512 x 2048 x 80 = 335 MB) is cut to a fixed, seeded sample of DUMP_SAMPLE_UTTS utterances in ascending order (31 MB at T = 2048)."""
+    os.makedirs(dirname, exist_ok=True)
+    mel = mel.detach()
+    if mel.numel() * 4 > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(mel.shape[0], DUMP_SAMPLE_UTTS, replace=False))
+        mel = mel[torch.as_tensor(idx, device=mel.device)]
+    np.save(os.path.join(dirname, 'mel.npy'), mel.float().cpu().numpy())
+
+
 def main_path(args):
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -1067,8 +1098,10 @@ def main_path(args):
     if rank == 0:
         assert out is not None and bool(torch.isfinite(out).all()), 'non-finite mel'
         assert out.shape == ((CFG5_UTTS, T, M) if cfg == 5 else (B, T, M)), out.shape
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out)
     scale_ref = None
-    if cfg == 5 and world > 1:
+    if cfg == 5 and world > 1 and args.full:
         # the same-workload N = 1 reference for whoever divides the N > 1 value: rank 0 samples ITS shard once more, alone and without the
         # gather, while the other ranks wait - the per-GPU rate of configs[4]; N x this is the ideal of the line above it
         if rank == 0:
@@ -1082,7 +1115,7 @@ def main_path(args):
                                  f'region, no gather: the per-GPU rate of BASELINE configs[4]; ideal at N={world} = {world} x this'}
         dist.barrier()
     per_rank = None
-    if cfg == 5:
+    if cfg == 5 and args.full:
         # every rank reports what IT did: its RCCL world, its shard (utterances, frames) and the wall time of that shard sampled once more,
         # all ranks at the same time, no gather - whoever reads the line sees imbalance or a slow device directly
         torch.cuda.synchronize()
@@ -1105,7 +1138,7 @@ def main_path(args):
     # stream every dsd_* call is enqueued on).  Persistent path: the kernel is k_loop, ONE launch = the whole 100-step loop
     # for one chunk of whole utterances (at most one workgroup per CU).
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         eng.prepare(cond)
         frames = B * T
         persistent = eng.loop_mode() == 1
@@ -1218,7 +1251,7 @@ def main_path(args):
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
             'higher_is_better': True, 'scaling': 'weak' if cfg == 2 else 'strong', 'vs_baseline': None,
             'dtype': 'f32 as 3 exact bf16 planes, 6 plane products per product, f32 accumulate (EXPERIMENT --split)' if args.split else 'f32',
-            'data': 'synthetic', 'config': conf, 'roofline': roof,
+            'data': 'synthetic', 'config': conf, **({'roofline': roof} if args.full else {}),
             'model_tflops_ref_accounting': frames_per_step * K * F_EVAL_REF * args.steps / el / 1e12,
         }
         res['workload_id'] = 'configs[1]: 8 x T=1024 per GPU (weak)' if cfg == 2 else f'configs[4]: {CFG5_UTTS} x T={CFG5_T} total (strong)'
@@ -1227,57 +1260,58 @@ def main_path(args):
             res['scale_ref_n1'] = scale_ref
         if per_rank is not None:
             res['per_rank'] = per_rank
-        try:
-            fixture = parity_check(device)
-        except Exception as e:          # fixtures missing etc. - report, do not hide
-            fixture = {'error': repr(e)}
-        if world == 1 and cfg == 2 and not args.no_cpu_baseline:
-            # ONE oracle run over the timed batch: the CPU rate of the workload and the parity of the kernel whose roofline is reported
-            last = count[0] & 1
-            res['cpu_baseline'], res['parity'], mel_oracle = cpu_baseline(gd, pre, conds[last], x_T, noise, out, roof['kernel'])
-            res['parity']['fixture'] = fixture
-            res['speedup_vs_cpu_baseline'] = value / res['cpu_baseline']['value']
+        if args.full:
             try:
-                res['torch_rocm_eager_baseline'] = torch_rocm_eager_baseline(gd, conds[last], x_T)
-                res['speedup_vs_torch_rocm_eager'] = value / res['torch_rocm_eager_baseline']['value']
-            except Exception as e:
-                res['torch_rocm_eager_baseline'] = {'error': repr(e)}
-            if not args.no_secondary and not args.split:
+                fixture = parity_check(device)
+            except Exception as e:          # fixtures missing etc. - report, do not hide
+                fixture = {'error': repr(e)}
+            if world == 1 and cfg == 2 and not args.no_cpu_baseline:
+                # ONE oracle run over the timed batch: the CPU rate of the workload and the parity of the kernel whose roofline is reported
+                last = count[0] & 1
+                res['cpu_baseline'], res['parity'], mel_oracle = cpu_baseline(gd, pre, conds[last], x_T, noise, out, roof['kernel'])
+                res['parity']['fixture'] = fixture
+                res['speedup_vs_cpu_baseline'] = value / res['cpu_baseline']['value']
                 try:
-                    res['secondary'] = secondary_split(gd, eng, pre, conds[last], x_T, noise, out, mel_oracle, args)
+                    res['torch_rocm_eager_baseline'] = torch_rocm_eager_baseline(gd, conds[last], x_T)
+                    res['speedup_vs_torch_rocm_eager'] = value / res['torch_rocm_eager_baseline']['value']
                 except Exception as e:
-                    res['secondary'] = {'error': repr(e)}
-        else:
-            res['parity'] = fixture
-        if world == 1 and cfg == 2 and not args.no_extras:
-            try:
-                res['inservice_noise'] = inservice_noise(gd, conds[0], x_T, K, B * T)
-                res['inservice_noise']['vs_explicit_noise'] = res['inservice_noise']['value'] / value
-            except Exception as e:
-                res['inservice_noise'] = {'error': repr(e)[:300]}
-            res['offshape'] = offshape(gd, device)
-        if world == 1 and cfg == 2 and not args.no_cfg5_shard:
-            # the N > 1 lines run BASELINE configs[4] (512 x T=2048, strong): one GPU's shard of the 8-GPU run - 64 utterances x T=2048 in
-            # micro-batches of 16, no gather - sampled here after everything else, so that a 1/2/4/8 curve can be normalised on ONE workload
-            # from the N = 1 line alone (value x 8 = the ideal of the N = 8 line)
-            try:
-                del conds, x_T, noise
-                torch.cuda.empty_cache()
-                _, local5, mine5, _, _, _ = cfg5_workload(gd, 0, 8, device)
-                local5()                                                   # warm: workspace growth to 16 x 2048, plan upload
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                local5()
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t0
-                res['cfg5_shard_n1'] = {'value': len(mine5) * CFG5_T / dt, 'unit': 'mel-frames/s', 'n_gpus': 1, 'seconds': dt,
-                                        'what': f"rank 0's shard of BASELINE configs[4] at 8 GPUs ({len(mine5)} of {CFG5_UTTS} utterances x T={CFG5_T}, "
-                                                f'micro-batches of {CFG5_MICRO}, K={K_STEPS}), no gather: the per-GPU rate of the workload the N > 1 '
-                                                f'lines run; N x this is their ideal'}
-            except Exception as e:
-                res['cfg5_shard_n1'] = {'error': repr(e)}
-        if world == 1 and cfg == 2 and not args.no_extras:
-            res['rows'] = quick_rows(gd, device)
+                    res['torch_rocm_eager_baseline'] = {'error': repr(e)}
+                if not args.no_secondary and not args.split:
+                    try:
+                        res['secondary'] = secondary_split(gd, eng, pre, conds[last], x_T, noise, out, mel_oracle, args)
+                    except Exception as e:
+                        res['secondary'] = {'error': repr(e)}
+            else:
+                res['parity'] = fixture
+            if world == 1 and cfg == 2 and not args.no_extras:
+                try:
+                    res['inservice_noise'] = inservice_noise(gd, conds[0], x_T, K, B * T)
+                    res['inservice_noise']['vs_explicit_noise'] = res['inservice_noise']['value'] / value
+                except Exception as e:
+                    res['inservice_noise'] = {'error': repr(e)[:300]}
+                res['offshape'] = offshape(gd, device)
+            if world == 1 and cfg == 2 and not args.no_cfg5_shard:
+                # the N > 1 lines run BASELINE configs[4] (512 x T=2048, strong): one GPU's shard of the 8-GPU run - 64 utterances x T=2048 in
+                # micro-batches of 16, no gather - sampled here after everything else, so that a 1/2/4/8 curve can be normalised on ONE workload
+                # from the N = 1 line alone (value x 8 = the ideal of the N = 8 line)
+                try:
+                    del conds, x_T, noise
+                    torch.cuda.empty_cache()
+                    _, local5, mine5, _, _, _ = cfg5_workload(gd, 0, 8, device)
+                    local5()                                                   # warm: workspace growth to 16 x 2048, plan upload
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    local5()
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    res['cfg5_shard_n1'] = {'value': len(mine5) * CFG5_T / dt, 'unit': 'mel-frames/s', 'n_gpus': 1, 'seconds': dt,
+                                            'what': f"rank 0's shard of BASELINE configs[4] at 8 GPUs ({len(mine5)} of {CFG5_UTTS} utterances x T={CFG5_T}, "
+                                                    f'micro-batches of {CFG5_MICRO}, K={K_STEPS}), no gather: the per-GPU rate of the workload the N > 1 '
+                                                    f'lines run; N x this is their ideal'}
+                except Exception as e:
+                    res['cfg5_shard_n1'] = {'error': repr(e)}
+            if world == 1 and cfg == 2 and not args.no_extras:
+                res['rows'] = quick_rows(gd, device)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

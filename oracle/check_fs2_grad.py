@@ -30,11 +30,10 @@ def loss_of(ret, seed):
     return total
 
 
-def main(name):
-    import torch
+def reference_gradients(name):
+    """The reference's side: {parameter: gradient} of its training forward on the seeded case, and the loss."""
     sys.path.insert(0, ROOT)
-    from oracle import fs2_oracle as FO
-    from oracle.fs2_cases import CASES, VOCAB
+    from oracle.fs2_cases import VOCAB
     from oracle.ref_driver import Reference
     from diffsinger_amd.synth import presets
     from tests import fs2_helpers as FH
@@ -53,21 +52,41 @@ def main(name):
     kw = {k: v.clone() for k, v in inp.items() if k != 'txt_tokens'}
     r = m(inp['txt_tokens'], skip_decoder=True, infer=False, **kw)
     loss_of(r, case['seed']).backward()
-    ref_grads = {k: v.grad.detach().clone() for k, v in m.named_parameters() if v.grad is not None}
+    return {k: v.grad.detach().clone() for k, v in m.named_parameters() if v.grad is not None}, float(loss_of(r, case['seed']).detach())
 
+
+def oracle_gradients(name):
+    """The oracle's side: {parameter: gradient} of torch autograd on oracle/fs2_oracle.py for the same case and functional, and the loss."""
+    import torch
+    sys.path.insert(0, ROOT)
+    from oracle import fs2_oracle as FO
+    from tests import fs2_helpers as FH
+    case, m_hip, hp_ours, params, inp = FH.case_setup(name)
     p = FH.oracle_params(params)
     kw = {k: v.clone() for k, v in inp.items() if k != 'txt_tokens'}
     o = FO.fs2_forward(p, hp_ours, inp['txt_tokens'], skip_decoder=True, **kw)
     loss_of(o, case['seed']).backward()
-    ora_grads = {k: v.grad for k, v in p.items() if torch.is_tensor(v) and v.is_floating_point() and v.grad is not None}
-    alias = {'encoder.embed_tokens.weight', 'encoder_embed_tokens.weight'}      # one tensor in the module, two keys in the state_dict / oracle
+    return {k: v.grad for k, v in p.items() if torch.is_tensor(v) and v.is_floating_point() and v.grad is not None}, float(loss_of(o, case['seed']).detach())
+
+
+ALIAS = {'encoder.embed_tokens.weight', 'encoder_embed_tokens.weight'}      # one tensor in the module, two keys in the state_dict / oracle
+
+
+def oracle_gradient_of(ora_grads, k):
+    """The oracle's gradient for the reference's parameter k (None if it has none)."""
+    if k in ALIAS:                                       # the oracle may hold the shared embedding as two leaves: their gradients add up
+        parts = [ora_grads[x] for x in ALIAS if x in ora_grads]
+        return sum(parts) if parts else None
+    return ora_grads.get(k)
+
+
+def main(name):
+    import torch
+    ref_grads, loss_ref = reference_gradients(name)
+    ora_grads, loss_ora = oracle_gradients(name)
     worst, n_bitequal, missing = ('', 0.0), 0, []
     for k, g in ref_grads.items():
-        if k in alias:                                   # the oracle may hold the shared embedding as two leaves: their gradients add up
-            parts = [ora_grads[x] for x in alias if x in ora_grads]
-            og = sum(parts) if parts else None
-        else:
-            og = ora_grads.get(k)
+        og = oracle_gradient_of(ora_grads, k)
         if og is None:
             missing.append(k)
             continue
@@ -76,7 +95,7 @@ def main(name):
         if e > worst[1]:
             worst = (k, e)
     res = {'case': name, 'parameters_with_gradient': len(ref_grads), 'bit_equal': n_bitequal, 'worst_rel_err': worst[1], 'worst_at': worst[0],
-           'missing_in_oracle': missing, 'loss_ref': float(loss_of(r, case['seed'])), 'loss_oracle': float(loss_of(o, case['seed']))}
+           'missing_in_oracle': missing, 'loss_ref': loss_ref, 'loss_oracle': loss_ora}
     print(json.dumps(res))
     return 0 if (not missing and worst[1] <= 1e-6) else 1
 

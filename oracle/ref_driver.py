@@ -1,7 +1,7 @@
 """Drive the REAL reference implementation (only where /root/reference is mounted: the build container).
 
-TEST INFRASTRUCTURE ONLY - used by `oracle/make_golden.py` (fixture generation) and
-`tests/test_oracle_vs_reference.py` (proves the restatement bit-equal to the reference).  Nothing here
+TEST INFRASTRUCTURE ONLY - used by `oracle/make_golden*.py` (fixture generation, among them the recorded live comparisons of
+`tests/test_oracle_vs_reference.py` and its kin: oracle/make_golden_live.py) and `oracle/check_fs2_grad.py`.  Nothing here
 is reachable from the product path, `bench.py` or the `-m gpu` tests: /root/reference does not exist on
 the GPU box.
 

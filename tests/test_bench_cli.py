@@ -3,6 +3,7 @@ import os
 import subprocess
 import sys
 
+import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -106,3 +107,47 @@ def test_the_n1_line_has_rows_offshape_and_inservice_noise_legs():
     assert bench.F_TRAIN_EXEC == 3 * (26_427_392 - 15_728_640 // 3) and bench.F_CONV_LAYERS == 15_728_640
     assert bench.WEIGHT_BYTES == 60_345_664 and bench.F_EVAL_EXEC_WINO == 15_810_560
     assert not [f for f in os.listdir(os.path.join(ROOT, 'tools')) if f.startswith('gpu_') and f.endswith('.sh')], 'ONE GPU script: tools/gpu.sh'
+
+
+def test_full_and_dump_outputs_flags(tmp_path, monkeypatch):
+    """A plain run is the timed steps alone; everything else the line can carry sits behind --full.  --dump-outputs writes the last timed
+    step's mel as float32, cut to a fixed, seeded sample of utterances when it is larger than 64 MB."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    r = _run('--help')
+    assert '--full' in r.stdout and '--dump-outputs' in r.stdout
+    r = _run('--steps', '0')
+    assert r.returncode != 0 and '--steps must be at least 1' in r.stderr
+    r = _run('--row', 'vocoder', '--dump-outputs', str(tmp_path))
+    assert r.returncode != 0 and 'cannot be combined with --row' in r.stderr
+    mel = torch.randn(3, 40, 80, generator=torch.Generator().manual_seed(1), dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / 'small'), mel)
+    got = np.load(tmp_path / 'small' / 'mel.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, mel.float().numpy())
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 100 * 40 * 80 * 4)
+    big = torch.arange(200 * 40 * 80, dtype=torch.float32).reshape(200, 40, 80)
+    for d in ('big1', 'big2'):
+        bench.dump_outputs(str(tmp_path / d), big)
+    a, b = np.load(tmp_path / 'big1' / 'mel.npy'), np.load(tmp_path / 'big2' / 'mel.npy')
+    assert a.shape == (bench.DUMP_SAMPLE_UTTS, 40, 80) and np.array_equal(a, b)
+    rows = a[:, 0, 0].astype(np.int64) // (40 * 80)
+    assert (np.diff(rows) > 0).all() and np.array_equal(a, big.numpy()[rows])
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dumped_outputs(tmp_path):
+    """The plain run: the headline fields, exactly --steps timed steps, no leg of --full, and the mel of the last step on disk."""
+    import json
+    import numpy as np
+    r = _run('--gpus', '1', '--steps', '2', '--warmup', '1', '--dump-outputs', str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in line, key
+    assert line['steps'] == 2 and line['warmup'] == 1 and line['unit'] == 'mel-frames/s' and line['dtype'] == 'f32'
+    assert abs(line['value'] * line['ms_per_step'] * 1e-3 - 8 * 1024) < 1e-3 * 8 * 1024
+    for key in ('roofline', 'parity', 'cpu_baseline', 'secondary', 'rows', 'offshape', 'inservice_noise', 'cfg5_shard_n1'):
+        assert key not in line, key
+    mel = np.load(tmp_path / 'mel.npy')
+    assert mel.shape == (8, 1024, 80) and mel.dtype == np.float32 and np.isfinite(mel).all()

@@ -1,65 +1,49 @@
-"""Row f2 groundwork (no HIP vocoder yet): the HiFi-GAN / NSF-HiFi-GAN generator oracle (oracle/hifigan_oracle.py) bit-for-bit
-against the live reference generator - with and without the NSF pitch source, before and after remove_weight_norm() - in the
-build container (skipped where /root/reference is absent)."""
+"""Row f2 groundwork: the HiFi-GAN / NSF-HiFi-GAN generator oracle (oracle/hifigan_oracle.py) bit-for-bit against what the live reference
+generator computed - with and without the NSF pitch source, before and after remove_weight_norm() - recorded in tests/golden/live_hifigan_*.npz
+by oracle/make_golden_live.py (build container): the reference's parameter tree, the digests of its weights in both forms and its waveforms."""
+import ast
 import os
-import subprocess
-import sys
 
 import pytest
 
-from oracle.ref_driver import reference_available
+from oracle.make_golden_live import digest, hifigan_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-CHILD = r'''
-import sys
-sys.path.insert(0, %(root)r)
-import numpy as np, torch
-from oracle.ref_driver import Reference
-from oracle import hifigan_oracle as HO
-ref = Reference('configs/tts/hifigan.yaml')
-import scipy.signal, scipy.signal.windows
-if not hasattr(scipy.signal, 'kaiser'):                   # modules/parallel_wavegan/layers/pqmf.py:12 imports the pre-1.13 name (unused here)
-    scipy.signal.kaiser = scipy.signal.windows.kaiser
-from modules.hifigan.hifigan import HifiGanGenerator
-h = dict(ref.hparams)
-h.update(use_pitch_embed=%(nsf)r, audio_sample_rate=24000, upsample_initial_channel=64, resblock=%(resblock)r)
-torch.manual_seed(11)
-m = HifiGanGenerator(h).eval()
-g = torch.Generator().manual_seed(5)
-with torch.no_grad():
-    for v in m.parameters():                              # init_weights is N(0, 0.01): make the signal path non-trivial
-        v.add_(0.05 * torch.randn(v.shape, generator=g))
-from diffsinger_amd.vocoder import HifiGanGenerator as HipGen            # the HIP module's parameter tree == the reference module's
-mine = HipGen(h)
-assert {k: tuple(v.shape) for k, v in mine.state_dict().items()} == {k: tuple(v.shape) for k, v in m.state_dict().items()}
-mine.load_state_dict(m.state_dict(), strict=True)
-B, T = 2, 37
-mel = torch.randn(B, 80, T, generator=g)
-f0 = None
-if %(nsf)r:
-    f0 = torch.rand(B, T, generator=g) * 300 + 80
-    f0[0, 10:15] = 0
-    f0[1, 30:] = 0
-for stage in ('weight_norm', 'plain'):
-    if stage == 'plain':
-        m.remove_weight_norm()
-    p = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    with torch.no_grad():
-        torch.manual_seed(99); a = m(mel, f0)
-        torch.manual_seed(99); b = HO.generator(p, h, mel, f0)
-    assert a.shape == (B, 1, T * 256), a.shape
-    assert torch.equal(a, b), (stage, float((a - b).abs().max()))
-print('HIFIGAN_EQUAL_OK', float(a.abs().max()))
-'''
 
-
-@pytest.mark.skipif(not reference_available(), reason='/root/reference not mounted')
 @pytest.mark.parametrize('resblock', ['1', '2'])
 @pytest.mark.parametrize('nsf', [False, True])
 def test_hifigan_oracle_bit_equal_to_live_reference(nsf, resblock):
-    res = subprocess.run([sys.executable, '-c', CHILD % dict(root=ROOT, nsf=nsf, resblock=resblock)], capture_output=True, text=True)
-    assert 'HIFIGAN_EQUAL_OK' in res.stdout, res.stdout[-2000:] + res.stderr[-3000:]
+    import numpy as np
+    import torch
+    from oracle import hifigan_oracle as HO
+    ref = np.load(os.path.join(ROOT, 'tests', 'golden', f'live_hifigan_{int(nsf)}_{resblock}.npz'))
+    h = ast.literal_eval(str(ref['h']))
+    assert h['use_pitch_embed'] == nsf and h['resblock'] == resblock
+    mine, g = hifigan_params(h)                          # the HIP module's parameter tree == the reference module's; the weights it was given
+    B, T = 2, 37
+    mel = torch.randn(B, 80, T, generator=g)
+    assert np.array_equal(mel.numpy(), ref['mel'])
+    f0 = None
+    if nsf:
+        f0 = torch.rand(B, T, generator=g) * 300 + 80
+        f0[0, 10:15] = 0
+        f0[1, 30:] = 0
+        assert np.array_equal(f0.numpy(), ref['f0'])
+    for stage in ('weight_norm', 'plain'):
+        if stage == 'plain':
+            mine.remove_weight_norm()
+        sd = mine.state_dict()
+        want = {k: (s, d) for k, s, d in zip(ref[f'{stage}_keys'], ref[f'{stage}_shapes'], ref[f'{stage}_digests'])}
+        assert {k: repr(tuple(v.shape)) for k, v in sd.items()} == {k: s for k, (s, _) in want.items()}, stage
+        for k, v in sd.items():                          # the oracle gets the reference's weights bit for bit
+            assert digest(v) == want[k][1], (stage, k)
+        p = {k: v.detach().clone() for k, v in sd.items()}
+        with torch.no_grad():
+            torch.manual_seed(99)
+            b = HO.generator(p, h, mel, f0)
+        assert b.shape == (B, 1, T * 256), b.shape
+        assert np.array_equal(b.numpy(), ref[f'{stage}_wav']), (stage, float(np.abs(b.numpy() - ref[f'{stage}_wav']).max()))
 
 
 @pytest.mark.parametrize('name', ['hifigan_plain', 'hifigan_nsf'])

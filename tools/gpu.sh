@@ -3,7 +3,7 @@
 # Results land in gpurun_out/<tag>/; every JSON summary carries the library's build id (dsd_build_id = sha256 of csrc/ + include/) and the tag.
 # Sections:
 #   suite      the whole GPU test suite + smoke()                        voc        vocoder tests + chain variants A/B + row bench + kernel stats
-#   bench      the driver's command (N = 1) + rocprofv3 kernel stats     vocpmc     PMC passes over the vocoder row's chain kernels
+#   bench      bench.py --full (N = 1) + rocprofv3 kernel stats          vocpmc     PMC passes over the vocoder row's chain kernels
 #   rows       bench.py --row vocoder | fs2 | train                      fs2        FastSpeech2 tests + row bench + kernel stats by grid
 #   looppmc    the three PMC passes over the headline kernel + timeline  train      training tests + row bench + kernel stats
 #   sweep      shape sweep + all-config throughput                       probes     machine ceilings (bare MFMA stream, HBM)
@@ -40,8 +40,8 @@ suite)
     python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
     tail -6 $O/pytest_gpu.txt | cut -c1-220; tail -3 $O/smoke.txt ;;
 bench)
-    timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
-    stats bench_n1 python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cfg5-shard --no-secondary --no-extras
+    timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
+    stats bench_n1 python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cfg5-shard --no-secondary --no-extras
     cut -c1-900 $O/bench_n1.json; tail -3 $O/bench_n1.err ;;
 rows)
     for row in vocoder fs2 train; do
