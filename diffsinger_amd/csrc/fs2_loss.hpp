@@ -1,0 +1,566 @@
+// fs2_loss.hpp - the training objective of FastSpeech2 (C ABI in include/dsf.h, "FastSpeech2 training objective"); included at the end of
+// dsd.hip (one translation unit: shares fail(), HIP_TRY).
+//
+// What is computed, and where the reference computes it (paths relative to the reference root):
+//   k_mel_loss_fwd / k_mel_loss_final   FastSpeech2Task.l1_loss and .ssim_loss (tasks/tts/fs2.py:160-178) on mel_out / target [B,T,M]:
+//               the masked L1 numerator, the SSIM map of (x + bias, y + bias) - modules/commons/ssim.py:330-351: an 11 x 11 Gaussian window
+//               (sigma 1.5, the 1-D weights of :319-327 in fp32) with ZERO padding of 5 on both axes, C1 = 0.01^2, C2 = 0.03^2 - weighted by
+//               weights_nonzero_speech(target) (tasks/tts/tts.py:124-128: a frame counts where any bin of the target is nonzero), and the
+//               weight count; one workgroup per (utterance, 16-frame tile) writes four partial sums, one workgroup adds them in a fixed order.
+//   k_mel_loss_bwd  d/d mel_out of lam_l1 L1 + lam_ssim (1 - SSIM) (and of the weighted mean of S, the ssim() drop-in): the five local
+//               statistics are recomputed from x and y with a halo of 10 frames, then
+//                   dx = G * a1 + 2 x (G * a11) + y (G * a12),   a1 / a11 / a12 = c dS/d mu1, c dS/d E11, c dS/d E12,
+//               c = dL/dS of the pixel; G symmetric and zero padded, so its adjoint is itself.  The L1 part is sign(x - y) (sign(0) = 0).
+//   k_dur_loss_rows / k_dur_loss_final  FastSpeech2Task.add_dur_loss (tasks/tts/fs2.py:180-219) and the MIDI tasks' add_dur_loss
+//               (usr/diffsinger_task.py:359-389, :443-473): mel2ph_to_dur as integer counts (modules/fastspeech/tts_modules.py:242-248),
+//               pdur / wdur / sdur, and (backward) their gradient wrt dur_pred.  Words are contiguous runs of phones under both segmentations,
+//               summed in phone order; the word buffer has T_txt entries, so nothing depends on the data's word count (no host sync).
+//
+// Every reduction has a fixed order (per-thread strided sums, then a tree): two evaluations are bitwise equal.  No float atomics.
+#pragma once
+
+namespace dsd {
+
+constexpr int kMlTile = 16;              // output frames per workgroup
+constexpr int kMlMaxM = 128;             // bins held in LDS per row
+constexpr int kDurMaxTxt = 2048;         // phones per utterance (LDS per workgroup: 9 words per phone)
+
+// gaussian(11, 1.5) of modules/commons/ssim.py:319-322 as torch computes it in fp32 (exp in double, rounded; normalised by the fp32 sum)
+__constant__ float kSsimG[11] = {
+    0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.106560p-2f,
+    0x1.b43c3ep-3f, 0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f};
+
+struct MelLossParams {
+    const float* x; const float* y;      // [B][T][M]: element strides sb / st, bins contiguous
+    long long xsb, xst, ysb, yst;
+    float* partial;                      // [B * ntile][4]
+    float* smap;                         // [B][T][M] contiguous, or null
+    const float* stats;                  // bwd: the forward's out[4]
+    const float* gout;                   // bwd: DEVICE [3], the upstream gradients of out[0..2]
+    const float* gmap;                   // bwd: [B][T][M] dL/dS, or null
+    float* dx;                           // bwd: [B][T][M] contiguous
+    int T, M, ntile, terms, weighted;    // terms: 1 L1, 2 SSIM
+    float bias, lam_l1, lam_ssim;
+};
+
+__device__ __forceinline__ float ml_sum256(float v, float* sh) {
+    __syncthreads();
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] = __fadd_rn(sh[threadIdx.x], sh[threadIdx.x + o]);
+        __syncthreads();
+    }
+    const float r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+// Vertical (frame-axis) 11-tap pass: output row r from rows [r, r + 10] of src [rows][M].
+__device__ __forceinline__ float ml_vtap(const float* src, int r, int m, int M) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) s = __fadd_rn(s, __fmul_rn(kSsimG[k], src[(r + k) * M + m]));
+    return s;
+}
+// Horizontal (bin-axis) 11-tap pass with zero padding outside [0, M).
+__device__ __forceinline__ float ml_htap(const float* src, int r, int m, int M) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) {
+        const int mm = m + k - 5;
+        const float v = (mm >= 0 && mm < M) ? src[r * M + mm] : 0.f;
+        s = __fadd_rn(s, __fmul_rn(kSsimG[k], v));
+    }
+    return s;
+}
+
+constexpr float kSsimC1 = (float)(0.01 * 0.01);
+constexpr float kSsimC2 = (float)(0.03 * 0.03);
+
+// k_mel_loss_fwd: grid (ntile, B), 256 threads; dynamic LDS: X, Y [26][M], V [5][16][M], row flags [16].
+__global__ __launch_bounds__(256) void k_mel_loss_fwd(MelLossParams p) {
+    extern __shared__ __attribute__((aligned(16))) float ml_sm[];
+    __shared__ float red[256];
+    const int M = p.M, T = p.T, tid = threadIdx.x;
+    const int b = blockIdx.y, t0 = blockIdx.x * kMlTile;
+    constexpr int R = kMlTile + 10;
+    const bool ssim = (p.terms & 2) != 0;
+    float* X = ml_sm;
+    float* Y = X + R * M;
+    float* V = Y + R * M;                                 // v1 | v2 | v11 | v22 | v12, each [kMlTile][M]
+    int* wrow = (int*)(V + 5 * kMlTile * M);
+    const float* xb = p.x + (long long)b * p.xsb;
+    const float* yb = p.y + (long long)b * p.ysb;
+    if (tid < kMlTile) wrow[tid] = p.weighted ? 0 : 1;
+    __syncthreads();
+    // rows t0 - 5 .. t0 + 20 (zero outside [0, T): the padding of F.conv2d, applied after the bias)
+    for (int i = tid; i < R * M; i += 256) {
+        const int r = i / M, m = i - r * M, t = t0 - 5 + r;
+        float xv = 0.f, yv = 0.f;
+        if (t >= 0 && t < T) {
+            const float xr = xb[(long long)t * p.xst + m], yr = yb[(long long)t * p.yst + m];
+            xv = __fadd_rn(xr, p.bias);
+            yv = __fadd_rn(yr, p.bias);
+            if (p.weighted && r >= 5 && r < 5 + kMlTile && yr != 0.f) atomicOr(&wrow[r - 5], 1);
+        }
+        X[i] = xv;
+        Y[i] = yv;
+    }
+    __syncthreads();
+    if (ssim) {
+        for (int i = tid; i < kMlTile * M; i += 256) {
+            const int r = i / M, m = i - r * M;
+            float s1 = 0.f, s2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) {
+                const float g = kSsimG[k];
+                const float xv = X[(r + k) * M + m], yv = Y[(r + k) * M + m];
+                s1 = __fadd_rn(s1, __fmul_rn(g, xv));
+                s2 = __fadd_rn(s2, __fmul_rn(g, yv));
+                s11 = __fadd_rn(s11, __fmul_rn(g, __fmul_rn(xv, xv)));
+                s22 = __fadd_rn(s22, __fmul_rn(g, __fmul_rn(yv, yv)));
+                s12 = __fadd_rn(s12, __fmul_rn(g, __fmul_rn(xv, yv)));
+            }
+            V[i] = s1; V[kMlTile * M + i] = s2; V[2 * kMlTile * M + i] = s11; V[3 * kMlTile * M + i] = s22; V[4 * kMlTile * M + i] = s12;
+        }
+        __syncthreads();
+    }
+    float a_l1 = 0.f, a_1ms = 0.f, a_s = 0.f;
+    for (int i = tid; i < kMlTile * M; i += 256) {
+        const int r = i / M, m = i - r * M, t = t0 + r;
+        if (t >= T) continue;
+        const float w = wrow[r] ? 1.f : 0.f;
+        if (p.terms & 1) {
+            const float d = __fsub_rn(xb[(long long)t * p.xst + m], yb[(long long)t * p.yst + m]);
+            a_l1 = __fadd_rn(a_l1, __fmul_rn(fabsf(d), w));
+        }
+        if (ssim) {
+            const float mu1 = ml_htap(V, r, m, M), mu2 = ml_htap(V + kMlTile * M, r, m, M);
+            const float e11 = ml_htap(V + 2 * kMlTile * M, r, m, M), e22 = ml_htap(V + 3 * kMlTile * M, r, m, M);
+            const float e12 = ml_htap(V + 4 * kMlTile * M, r, m, M);
+            const float mu1_sq = __fmul_rn(mu1, mu1), mu2_sq = __fmul_rn(mu2, mu2), mu12 = __fmul_rn(mu1, mu2);
+            const float s1 = __fsub_rn(e11, mu1_sq), s2 = __fsub_rn(e22, mu2_sq), s12 = __fsub_rn(e12, mu12);
+            const float num = __fmul_rn(__fadd_rn(__fmul_rn(2.f, mu12), kSsimC1), __fadd_rn(__fmul_rn(2.f, s12), kSsimC2));
+            const float den = __fmul_rn(__fadd_rn(__fadd_rn(mu1_sq, mu2_sq), kSsimC1), __fadd_rn(__fadd_rn(s1, s2), kSsimC2));
+            const float S = __fdiv_rn(num, den);
+            if (p.smap) p.smap[((long long)b * T + t) * M + m] = S;
+            a_1ms = __fadd_rn(a_1ms, __fmul_rn(__fsub_rn(1.f, S), w));
+            a_s = __fadd_rn(a_s, __fmul_rn(S, w));
+        }
+    }
+    const float t_l1 = ml_sum256(a_l1, red), t_1ms = ml_sum256(a_1ms, red), t_s = ml_sum256(a_s, red);
+    if (tid == 0) {
+        int rows = 0;
+        for (int r = 0; r < kMlTile && t0 + r < T; ++r) rows += wrow[r];
+        float* o = p.partial + ((long long)b * p.ntile + blockIdx.x) * 4;
+        o[0] = t_l1; o[1] = t_1ms; o[2] = t_s; o[3] = (float)(rows * M);
+    }
+}
+
+// k_mel_loss_final: one workgroup; out = [lam_l1 * L1, lam_ssim * (1 - SSIM), mean S, weight count], each a quotient by the count
+// (the reference's (l * weights).sum() / weights.sum(), then * lambda).
+__global__ __launch_bounds__(256) void k_mel_loss_final(const float* __restrict__ partial, int n, float lam_l1, float lam_ssim, float* __restrict__ out) {
+    __shared__ float red[256];
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < n; i += 256)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] = __fadd_rn(a[q], partial[(long long)i * 4 + q]);
+    float tot[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tot[q] = ml_sum256(a[q], red);
+    if (threadIdx.x == 0) {
+        const float cnt = tot[3];
+        out[0] = __fmul_rn(__fdiv_rn(tot[0], cnt), lam_l1);
+        out[1] = __fmul_rn(__fdiv_rn(tot[1], cnt), lam_ssim);
+        out[2] = __fdiv_rn(tot[2], cnt);
+        out[3] = cnt;
+    }
+}
+
+// k_mel_loss_bwd: grid (ntile, B), 256 threads; dynamic LDS: region P = X, Y [36][M] and later A [3][26][M]; region Q = V [5][26][M] and
+// later U [3][16][M]; row flags [26].
+__global__ __launch_bounds__(256) void k_mel_loss_bwd(MelLossParams p) {
+    extern __shared__ __attribute__((aligned(16))) float ml_sm[];
+    const int M = p.M, T = p.T, tid = threadIdx.x;
+    const int b = blockIdx.y, t0 = blockIdx.x * kMlTile;
+    constexpr int R2 = kMlTile + 20, R1 = kMlTile + 10;
+    const bool ssim = (p.terms & 2) != 0;
+    const int pn = (2 * R2 > 3 * R1 ? 2 * R2 : 3 * R1) * M;
+    float* X = ml_sm;
+    float* Y = X + R2 * M;
+    float* A = ml_sm;                                     // a1 | a11 | a12, each [R1][M] (after X, Y are consumed)
+    float* V = ml_sm + pn;                                // v1 | v2 | v11 | v22 | v12, each [R1][M]
+    float* U = V;                                         // u1 | u11 | u12, each [kMlTile][M] (after V is consumed)
+    int* wrow = (int*)(V + 5 * R1 * M);                   // frames t0 - 5 .. t0 + 20
+    const float* xb = p.x + (long long)b * p.xsb;
+    const float* yb = p.y + (long long)b * p.ysb;
+    const float cnt = p.stats[3];
+    const float c_l1 = __fdiv_rn(__fmul_rn(p.lam_l1, p.gout[0]), cnt);
+    const float c_s = __fdiv_rn(__fsub_rn(p.gout[2], __fmul_rn(p.lam_ssim, p.gout[1])), cnt);
+    if (tid < R1) wrow[tid] = p.weighted ? 0 : 1;
+    __syncthreads();
+    for (int i = tid; i < R2 * M; i += 256) {
+        const int r = i / M, m = i - r * M, t = t0 - 10 + r;
+        float xv = 0.f, yv = 0.f;
+        if (t >= 0 && t < T) {
+            const float yr = yb[(long long)t * p.yst + m];
+            xv = __fadd_rn(xb[(long long)t * p.xst + m], p.bias);
+            yv = __fadd_rn(yr, p.bias);
+            if (p.weighted && r >= 5 && r < 5 + R1 && yr != 0.f) atomicOr(&wrow[r - 5], 1);
+        }
+        X[i] = xv;
+        Y[i] = yv;
+    }
+    __syncthreads();
+    if (ssim) {
+        for (int i = tid; i < R1 * M; i += 256) {
+            const int r = i / M, m = i - r * M;
+            float s1 = 0.f, s2 = 0.f, s11 = 0.f, s22 = 0.f, s12 = 0.f;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) {
+                const float g = kSsimG[k];
+                const float xv = X[(r + k) * M + m], yv = Y[(r + k) * M + m];
+                s1 = __fadd_rn(s1, __fmul_rn(g, xv));
+                s2 = __fadd_rn(s2, __fmul_rn(g, yv));
+                s11 = __fadd_rn(s11, __fmul_rn(g, __fmul_rn(xv, xv)));
+                s22 = __fadd_rn(s22, __fmul_rn(g, __fmul_rn(yv, yv)));
+                s12 = __fadd_rn(s12, __fmul_rn(g, __fmul_rn(xv, yv)));
+            }
+            V[i] = s1; V[R1 * M + i] = s2; V[2 * R1 * M + i] = s11; V[3 * R1 * M + i] = s22; V[4 * R1 * M + i] = s12;
+        }
+        __syncthreads();
+        // a1 / a11 / a12 on frames t0 - 5 .. t0 + 20 (zero outside [0, T): no output pixel there)
+        for (int i = tid; i < R1 * M; i += 256) {
+            const int r = i / M, m = i - r * M, t = t0 - 5 + r;
+            float a1 = 0.f, a11 = 0.f, a12 = 0.f;
+            if (t >= 0 && t < T) {
+                const long long px = ((long long)b * T + t) * M + m;
+                float c = wrow[r] ? c_s : 0.f;
+                if (p.gmap) c = __fadd_rn(c, p.gmap[px]);
+                const float mu1 = ml_htap(V, r, m, M), mu2 = ml_htap(V + R1 * M, r, m, M);
+                const float e11 = ml_htap(V + 2 * R1 * M, r, m, M), e22 = ml_htap(V + 3 * R1 * M, r, m, M);
+                const float e12 = ml_htap(V + 4 * R1 * M, r, m, M);
+                const float mu1_sq = __fmul_rn(mu1, mu1), mu2_sq = __fmul_rn(mu2, mu2), mu12 = __fmul_rn(mu1, mu2);
+                const float s1 = __fsub_rn(e11, mu1_sq), s2 = __fsub_rn(e22, mu2_sq), s12 = __fsub_rn(e12, mu12);
+                const float An = __fadd_rn(__fmul_rn(2.f, mu12), kSsimC1), Bn = __fadd_rn(__fmul_rn(2.f, s12), kSsimC2);
+                const float Cd = __fadd_rn(__fadd_rn(mu1_sq, mu2_sq), kSsimC1), D = __fadd_rn(__fadd_rn(s1, s2), kSsimC2);
+                const float inv_cd = __fdiv_rn(1.f, Cd), inv_d = __fdiv_rn(1.f, D);
+                const float inv_den = __fmul_rn(inv_cd, inv_d);
+                const float S = __fmul_rn(__fmul_rn(An, Bn), inv_den);
+                // dS/dmu1 = 2 mu2 (Bn - An) / (Cd D) - 2 mu1 S (1/Cd - 1/D);  dS/dE11 = -S / D;  dS/dE12 = 2 An / (Cd D)
+                const float dmu1 = __fsub_rn(__fmul_rn(__fmul_rn(2.f, mu2), __fmul_rn(__fsub_rn(Bn, An), inv_den)),
+                                             __fmul_rn(__fmul_rn(2.f, mu1), __fmul_rn(S, __fsub_rn(inv_cd, inv_d))));
+                a1 = __fmul_rn(c, dmu1);
+                a11 = -__fmul_rn(c, __fmul_rn(S, inv_d));
+                a12 = __fmul_rn(c, __fmul_rn(__fmul_rn(2.f, An), inv_den));
+            }
+            // X / Y are dead (the V pass above was the last reader, behind a barrier): A overwrites them
+            A[i] = a1; A[R1 * M + i] = a11; A[2 * R1 * M + i] = a12;
+        }
+        __syncthreads();
+        for (int i = tid; i < kMlTile * M; i += 256) {            // V is dead (its last reader was behind the barrier): U takes its place
+            const int r = i / M, m = i - r * M;
+            U[i] = ml_vtap(A, r, m, M);
+            U[kMlTile * M + i] = ml_vtap(A + R1 * M, r, m, M);
+            U[2 * kMlTile * M + i] = ml_vtap(A + 2 * R1 * M, r, m, M);
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < kMlTile * M; i += 256) {
+        const int r = i / M, m = i - r * M, t = t0 + r;
+        if (t >= T) continue;
+        const float xr = xb[(long long)t * p.xst + m], yr = yb[(long long)t * p.yst + m];
+        float g = 0.f;
+        if (ssim) {
+            const float h1 = ml_htap(U, r, m, M), h11 = ml_htap(U + kMlTile * M, r, m, M), h12 = ml_htap(U + 2 * kMlTile * M, r, m, M);
+            const float xv = __fadd_rn(xr, p.bias), yv = __fadd_rn(yr, p.bias);
+            g = __fadd_rn(__fadd_rn(h1, __fmul_rn(__fmul_rn(2.f, xv), h11)), __fmul_rn(yv, h12));
+        }
+        if ((p.terms & 1) && wrow[r + 5]) {
+            const float d = __fsub_rn(xr, yr);
+            const float sg = (d > 0.f) ? 1.f : (d < 0.f) ? -1.f : d;               // torch.sign: 0 at 0, NaN stays NaN
+            g = __fadd_rn(g, __fmul_rn(c_l1, sg));
+        }
+        p.dx[((long long)b * T + t) * M + m] = g;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// duration terms
+// ------------------------------------------------------------------------------------------------------------
+struct DurLossParams {
+    const float* dur_pred;               // [B][Tt] log domain
+    const long long* mel2ph;             // [B][T]
+    const long long* tokens;             // [B][Tt]
+    const long long* sil_ids;            // segmentation (a): silence-phone ids [n_sil]
+    const long long* wdb;                // segmentation (b): word_boundary [B][Tt]
+    float* ws;                           // [B][8] row sums, then [8] totals
+    float* out;                          // [3]: pdur, wdur, sdur
+    const float* gout;                   // bwd: DEVICE [3]
+    float* grad;                         // bwd: [B][Tt]
+    int B, Tt, T, n_sil;
+    float lam_p, lam_w, lam_s;
+};
+constexpr int kDurRow = 8;               // floats per row in ws: pnum, pcnt, wnum, wcnt, sterm, bad
+
+// k_dur_loss_rows<BWD>: one workgroup per utterance, 256 threads; dynamic LDS of 9 * Tt + 1 words.
+template <bool BWD>
+__global__ __launch_bounds__(256) void k_dur_loss_rows(DurLossParams p) {
+    extern __shared__ __attribute__((aligned(16))) float dl_sm[];
+    __shared__ float red[256];
+    __shared__ int itot[256];
+    __shared__ int bad;
+    const int Tt = p.Tt, T = p.T, tid = threadIdx.x, b = blockIdx.x;
+    int* cnt = (int*)dl_sm;                  // [Tt + 1] frames per phone (index 0: padding frames)
+    int* raw = cnt + Tt + 1;                 // [Tt] silence flag (a) / word_boundary (b)
+    int* cs = raw + Tt;                      // [Tt] inclusive prefix sums of raw
+    int* word = cs + Tt;                     // [Tt] word slot in [0, Tt), -1: not in any kept word
+    float* lin = (float*)(word + Tt);        // [Tt] (exp(d) - 1).clamp(min=0)
+    float* gt = lin + Tt;                    // [Tt] dur_gt
+    float* P = gt + Tt;                      // [Tt] word_dur_p by slot
+    float* G = P + Tt;                       // [Tt] word_dur_g by slot
+    float* D = G + Tt;                       // [Tt] dur_pred
+    if (tid == 0) bad = 0;
+    for (int i = tid; i <= Tt; i += 256) cnt[i] = 0;
+    __syncthreads();
+    for (int t = tid; t < T; t += 256) {
+        const long long v = p.mel2ph[(long long)b * T + t];
+        if (v < 0 || v > Tt) bad = 1;                                       // the reference's scatter_add raises
+        else atomicAdd(&cnt[v], 1);
+    }
+    // per phone
+    float a_p = 0.f, a_np = 0.f;
+    for (int i = tid; i < Tt; i += 256) {
+        const long long tok = p.tokens[(long long)b * Tt + i];
+        int r;
+        if (p.wdb) {
+            const long long w = p.wdb[(long long)b * Tt + i];
+            if (w < 0 || w > Tt) bad = 1;
+            r = (int)(w < 0 ? 0 : w > Tt ? Tt : w);
+        } else {
+            r = 0;
+            for (int k = 0; k < p.n_sil; ++k) r |= (tok == p.sil_ids[k]);
+        }
+        raw[i] = r;
+        D[i] = p.dur_pred[(long long)b * Tt + i];
+        P[i] = 0.f;
+        G[i] = 0.f;
+    }
+    __syncthreads();
+    for (int i = tid; i < Tt; i += 256) {
+        const float np = p.tokens[(long long)b * Tt + i] != 0 ? 1.f : 0.f;
+        const float g = __fmul_rn((float)cnt[i + 1], np);
+        const float d = D[i];
+        const float e = __fsub_rn(d, logf(__fadd_rn(g, 1.f)));
+        a_p = __fadd_rn(a_p, __fmul_rn(__fmul_rn(e, e), np));
+        a_np = __fadd_rn(a_np, np);
+        const float l = __fsub_rn(expf(d), 1.f);
+        lin[i] = l < 0.f ? 0.f : l;                                         // clamp(min=0): NaN stays NaN
+        gt[i] = g;
+    }
+    // inclusive scan of raw -> cs (chunk per thread, then the 256 chunk totals)
+    const int chunk = (Tt + 255) / 256, c0 = tid * chunk, c1 = min(Tt, c0 + chunk);
+    int run = 0;
+    for (int i = c0; i < c1; ++i) { run += raw[i]; cs[i] = run; }
+    itot[tid] = run;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int v = tid >= o ? itot[tid - o] : 0;
+        __syncthreads();
+        itot[tid] += v;
+        __syncthreads();
+    }
+    const int off = tid > 0 ? itot[tid - 1] : 0;
+    for (int i = c0; i < c1; ++i) cs[i] += off;
+    __syncthreads();
+    for (int i = tid; i < Tt; i += 256) {
+        int s;
+        if (p.wdb) {
+            s = cs[i] - raw[i];                                             // F.pad(cumsum(wdb), (1, 0))[:, :-1]: every word kept
+            if (s >= Tt) { bad = 1; s = Tt - 1; }                         // word_boundary > 1: more words than phones
+        } else {
+            s = raw[i] ? -1 : cs[i] - 1;                                    // cumsum(is_sil) * (1 - is_sil), word 0 dropped
+        }
+        word[i] = s;
+    }
+    __syncthreads();
+    // words are contiguous runs of phones: the first phone of a run sums it in phone order
+    float a_w = 0.f, a_m = 0.f;
+    for (int i = tid; i < Tt; i += 256) {
+        const int s = word[i];
+        if (s < 0 || (i > 0 && word[i - 1] == s)) continue;
+        float sp = 0.f, sg = 0.f;
+        for (int j = i; j < Tt && word[j] == s; ++j) { sp = __fadd_rn(sp, lin[j]); sg = __fadd_rn(sg, gt[j]); }
+        P[s] = sp;
+        G[s] = sg;
+        const float m = sg > 0.f ? 1.f : 0.f;
+        const float e = __fsub_rn(logf(__fadd_rn(sp, 1.f)), logf(__fadd_rn(sg, 1.f)));
+        a_w = __fadd_rn(a_w, __fmul_rn(__fmul_rn(e, e), m));
+        a_m = __fadd_rn(a_m, m);
+    }
+    float a_sp = 0.f, a_sg = 0.f;
+    for (int i = tid; i < Tt; i += 256) { a_sp = __fadd_rn(a_sp, lin[i]); a_sg = __fadd_rn(a_sg, gt[i]); }
+    const float S = ml_sum256(a_sp, red), Sg = ml_sum256(a_sg, red);
+    const float es = __fsub_rn(logf(__fadd_rn(S, 1.f)), logf(__fadd_rn(Sg, 1.f)));
+    if (!BWD) {
+        const float pn = ml_sum256(a_p, red), pc = ml_sum256(a_np, red), wn = ml_sum256(a_w, red), wc = ml_sum256(a_m, red);
+        if (tid == 0) {
+            float* o = p.ws + (long long)b * kDurRow;
+            o[0] = pn; o[1] = pc; o[2] = wn; o[3] = wc; o[4] = __fmul_rn(es, es); o[5] = bad ? 1.f : 0.f;
+        }
+        return;
+    }
+    __syncthreads();                                                       // P / G of every slot written
+    const float* tot = p.ws + (long long)p.B * kDurRow;                      // pcnt, wcnt, bad (k_dur_loss_final)
+    const float nanv = __int_as_float(0x7fc00000);
+    const float cp = __fdiv_rn(__fmul_rn(__fmul_rn(p.gout[0], p.lam_p), 2.f), tot[0]);
+    const float cw = __fdiv_rn(__fmul_rn(__fmul_rn(p.gout[1], p.lam_w), 2.f), tot[1]);
+    const float csd = __fdiv_rn(__fmul_rn(__fmul_rn(__fmul_rn(p.gout[2], p.lam_s), 2.f), es), __fmul_rn(__fadd_rn(S, 1.f), (float)p.B));
+    for (int i = tid; i < Tt; i += 256) {
+        const float np = p.tokens[(long long)b * Tt + i] != 0 ? 1.f : 0.f;
+        const float d = D[i], g = gt[i];
+        float gd = __fmul_rn(__fmul_rn(cp, __fsub_rn(d, logf(__fadd_rn(g, 1.f)))), np);
+        float gl = csd;
+        const int s = word[i];
+        if (s >= 0) {
+            const float sp = P[s], sg = G[s];
+            const float m = sg > 0.f ? 1.f : 0.f;
+            const float e = __fsub_rn(logf(__fadd_rn(sp, 1.f)), logf(__fadd_rn(sg, 1.f)));
+            gl = __fadd_rn(gl, __fdiv_rn(__fmul_rn(__fmul_rn(cw, e), m), __fadd_rn(sp, 1.f)));
+        }
+        const float ex = expf(d);
+        const float dl = (__fsub_rn(ex, 1.f) >= 0.f) ? ex : 0.f;            // clamp_min's backward passes where input >= min
+        gd = __fadd_rn(gd, __fmul_rn(gl, dl));
+        p.grad[(long long)b * Tt + i] = (bad || tot[2] != 0.f) ? nanv : gd;
+    }
+}
+
+// k_dur_loss_final: one workgroup; sums the rows in utterance order.  Any mel2ph (or word_boundary) value outside its range: NaN losses.
+__global__ __launch_bounds__(64) void k_dur_loss_final(DurLossParams p) {
+    if (threadIdx.x != 0) return;
+    float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < p.B; ++b)
+        for (int q = 0; q < 6; ++q) s[q] = __fadd_rn(s[q], p.ws[(long long)b * kDurRow + q]);
+    const float nanv = __int_as_float(0x7fc00000);
+    const bool bad = s[5] != 0.f;
+    p.out[0] = bad ? nanv : __fmul_rn(__fdiv_rn(s[0], s[1]), p.lam_p);
+    p.out[1] = bad ? nanv : __fmul_rn(__fdiv_rn(s[2], s[3]), p.lam_w);
+    p.out[2] = bad ? nanv : __fmul_rn(__fdiv_rn(s[4], (float)p.B), p.lam_s);
+    float* tot = p.ws + (long long)p.B * kDurRow;
+    tot[0] = s[1]; tot[1] = s[3]; tot[2] = s[5];
+}
+
+}  // namespace dsd
+
+// ------------------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------------------
+static inline size_t ml_lds_fwd(int M) { return ((size_t)2 * (kMlTile + 10) * M + (size_t)5 * kMlTile * M) * 4 + kMlTile * 4; }
+static inline size_t ml_lds_bwd(int M) {
+    const int R2 = kMlTile + 20, R1 = kMlTile + 10;
+    return ((size_t)std::max(2 * R2, 3 * R1) * M + (size_t)5 * R1 * M) * 4 + R1 * 4;
+}
+static inline size_t dl_lds(int Tt) { return ((size_t)9 * Tt + 1) * 4; }
+// dynamic LDS beyond 64 KiB must be allowed per kernel (M = 128: 68 / 107 KiB; T_txt = 2048: 74 KiB)
+static int fl_lds_attr() {
+    static bool done = false;
+    if (!done) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_mel_loss_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ml_lds_fwd(kMlMaxM)));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_mel_loss_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ml_lds_bwd(kMlMaxM)));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_dur_loss_rows<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dl_lds(kDurMaxTxt)));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_dur_loss_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dl_lds(kDurMaxTxt)));
+        done = true;
+    }
+    return DSD_OK;
+}
+
+extern "C" int64_t dsf_fs2_loss_workspace_floats(int32_t B, int32_t T, int32_t which) {
+    if (B < 1 || B > 65535 || T < 1) return -1;
+    if (which == 0) return (int64_t)B * ((T + kMlTile - 1) / kMlTile) * 4;
+    if (which == 1) return (int64_t)B * kDurRow + 8;
+    return -1;
+}
+
+static int ml_check(const char* who, const float* x, const float* y, int32_t B, int32_t T, int32_t M, int32_t terms) {
+    if (!x || !y || B < 1 || B > 65535 || T < 1 || T > (1 << 26) || M < 1 || M > kMlMaxM || terms < 1 || terms > 3)
+        return fail(DSD_ERR_INVALID, "%s: bad argument (B=%d T=%d M=%d terms=%d; 1 <= M <= %d, terms 1 (L1) | 2 (SSIM))", who, B, T, M, terms, kMlMaxM);
+    return DSD_OK;
+}
+
+extern "C" int dsf_mel_loss(const float* x, int64_t x_sb, int64_t x_st, const float* y, int64_t y_sb, int64_t y_st, int32_t B, int32_t T, int32_t M,
+                            float bias, int32_t weighted, int32_t terms, float lam_l1, float lam_ssim, float* ssim_map, float* workspace, float* out,
+                            void* stream) {
+    DSD_TRY(ml_check("dsf_mel_loss", x, y, B, T, M, terms));
+    if (!workspace || !out || (ssim_map && !(terms & 2))) return fail(DSD_ERR_INVALID, "dsf_mel_loss: workspace / out missing, or a map without the SSIM term");
+    MelLossParams p{};
+    p.x = x; p.y = y; p.xsb = x_sb; p.xst = x_st; p.ysb = y_sb; p.yst = y_st;
+    p.partial = workspace; p.smap = ssim_map;
+    p.T = T; p.M = M; p.ntile = (T + kMlTile - 1) / kMlTile; p.terms = terms; p.weighted = weighted ? 1 : 0;
+    p.bias = bias; p.lam_l1 = lam_l1; p.lam_ssim = lam_ssim;
+    DSD_TRY(fl_lds_attr());
+    hipLaunchKernelGGL(k_mel_loss_fwd, dim3((unsigned)p.ntile, (unsigned)B), dim3(256), ml_lds_fwd(M), (hipStream_t)stream, p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_mel_loss_final, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, B * p.ntile, lam_l1, lam_ssim, out);
+    HIP_TRY(hipGetLastError());
+    return DSD_OK;
+}
+
+extern "C" int dsf_mel_loss_bwd(const float* x, int64_t x_sb, int64_t x_st, const float* y, int64_t y_sb, int64_t y_st, int32_t B, int32_t T, int32_t M,
+                                float bias, int32_t weighted, int32_t terms, float lam_l1, float lam_ssim, const float* stats, const float* grad_out,
+                                const float* grad_map, float* dx, void* stream) {
+    DSD_TRY(ml_check("dsf_mel_loss_bwd", x, y, B, T, M, terms));
+    if (!stats || !grad_out || !dx || (grad_map && !(terms & 2))) return fail(DSD_ERR_INVALID, "dsf_mel_loss_bwd: stats / grad_out / dx missing, or a map without the SSIM term");
+    MelLossParams p{};
+    p.x = x; p.y = y; p.xsb = x_sb; p.xst = x_st; p.ysb = y_sb; p.yst = y_st;
+    p.stats = stats; p.gout = grad_out; p.gmap = grad_map; p.dx = dx;
+    p.T = T; p.M = M; p.ntile = (T + kMlTile - 1) / kMlTile; p.terms = terms; p.weighted = weighted ? 1 : 0;
+    p.bias = bias; p.lam_l1 = lam_l1; p.lam_ssim = lam_ssim;
+    DSD_TRY(fl_lds_attr());
+    hipLaunchKernelGGL(k_mel_loss_bwd, dim3((unsigned)p.ntile, (unsigned)B), dim3(256), ml_lds_bwd(M), (hipStream_t)stream, p);
+    HIP_TRY(hipGetLastError());
+    return DSD_OK;
+}
+
+static int dl_params(const char* who, DurLossParams& p, const float* dur_pred, const int64_t* mel2ph, const int64_t* txt_tokens, const int64_t* sil_ids,
+                     int32_t n_sil, const int64_t* word_boundary, int32_t B, int32_t T_txt, int32_t T, float lam_ph, float lam_word, float lam_sent,
+                     float* workspace) {
+    if (!dur_pred || !mel2ph || !txt_tokens || !workspace || B < 1 || B > 65535 || T_txt < 1 || T_txt > kDurMaxTxt || T < 1 || n_sil < 0 ||
+        (word_boundary && sil_ids) || (!word_boundary && n_sil > 0 && !sil_ids))
+        return fail(DSD_ERR_INVALID, "%s: bad argument (B=%d T_txt=%d T=%d n_sil=%d; T_txt <= %d; silence ids or word_boundary, not both)", who, B, T_txt,
+                    T, n_sil, kDurMaxTxt);
+    p = DurLossParams{};
+    p.dur_pred = dur_pred; p.mel2ph = (const long long*)mel2ph; p.tokens = (const long long*)txt_tokens;
+    p.sil_ids = (const long long*)sil_ids; p.n_sil = word_boundary ? 0 : n_sil; p.wdb = (const long long*)word_boundary;
+    p.ws = workspace; p.B = B; p.Tt = T_txt; p.T = T; p.lam_p = lam_ph; p.lam_w = lam_word; p.lam_s = lam_sent;
+    return DSD_OK;
+}
+
+extern "C" int dsf_dur_loss(const float* dur_pred, const int64_t* mel2ph, const int64_t* txt_tokens, const int64_t* sil_ids, int32_t n_sil,
+                            const int64_t* word_boundary, int32_t B, int32_t T_txt, int32_t T, float lam_ph, float lam_word, float lam_sent,
+                            float* workspace, float* out, void* stream) {
+    DurLossParams p;
+    DSD_TRY(dl_params("dsf_dur_loss", p, dur_pred, mel2ph, txt_tokens, sil_ids, n_sil, word_boundary, B, T_txt, T, lam_ph, lam_word, lam_sent, workspace));
+    if (!out) return fail(DSD_ERR_INVALID, "dsf_dur_loss: out missing");
+    p.out = out;
+    DSD_TRY(fl_lds_attr());
+    hipLaunchKernelGGL(k_dur_loss_rows<false>, dim3((unsigned)B), dim3(256), dl_lds(T_txt), (hipStream_t)stream, p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_dur_loss_final, dim3(1), dim3(64), 0, (hipStream_t)stream, p);
+    HIP_TRY(hipGetLastError());
+    return DSD_OK;
+}
+
+extern "C" int dsf_dur_loss_bwd(const float* dur_pred, const int64_t* mel2ph, const int64_t* txt_tokens, const int64_t* sil_ids, int32_t n_sil,
+                                const int64_t* word_boundary, int32_t B, int32_t T_txt, int32_t T, float lam_ph, float lam_word, float lam_sent,
+                                const float* workspace, const float* grad_out, float* grad, void* stream) {
+    DurLossParams p;
+    DSD_TRY(dl_params("dsf_dur_loss_bwd", p, dur_pred, mel2ph, txt_tokens, sil_ids, n_sil, word_boundary, B, T_txt, T, lam_ph, lam_word, lam_sent,
+                      (float*)workspace));
+    if (!grad_out || !grad) return fail(DSD_ERR_INVALID, "dsf_dur_loss_bwd: grad_out / grad missing");
+    p.gout = grad_out; p.grad = grad;
+    DSD_TRY(fl_lds_attr());
+    hipLaunchKernelGGL(k_dur_loss_rows<true>, dim3((unsigned)B), dim3(256), dl_lds(T_txt), (hipStream_t)stream, p);
+    HIP_TRY(hipGetLastError());
+    return DSD_OK;
+}

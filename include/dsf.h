@@ -272,6 +272,36 @@ int dsf_channel_affine(const float* x, const float* a, const float* b, const flo
 int dsf_group_norm(const float* x, const float* gamma, const float* beta, const float* residual, float* y, int32_t B, int32_t C, int32_t groups,
                    int32_t T, float eps, int32_t relu, void* stream);
 
+/* FastSpeech2 training objective (tasks/tts/fs2.py:111-283; usr/diffsinger_task.py:359-389, :443-473), forward and backward; no allocation, no
+ * synchronisation, every sum in a fixed order (two evaluations are bitwise equal).  Workspaces: dsf_fs2_loss_workspace_floats(B, T, 0) floats for
+ * the mel terms (T = frames), (B, T_txt, 1) for the duration terms; the backward of the duration terms reads what its forward left there.
+ * dsf_mel_loss       x = mel_out, y = target [B][T][M] fp32 (element strides *_sb / *_st, the M bins contiguous; 1 <= M <= 128; T >= 1):
+ *                    out[0] = lam_l1 * FastSpeech2Task.l1_loss (:160-167), out[1] = lam_ssim * .ssim_loss (:169-178: 1 - SSIM of x + bias,
+ *                    y + bias, modules/commons/ssim.py:330-351 with the 11 x 11 Gaussian window, sigma 1.5, zero padding 5), out[2] = the
+ *                    weighted mean of the SSIM map, out[3] = the weight count; weighted = 1: a frame counts where any bin of y is nonzero
+ *                    (weights_nonzero_speech, tasks/tts/tts.py:124-128), 0: every pixel counts.  terms: 1 L1, 2 SSIM, 3 both (a term not
+ *                    asked for reads 0).  ssim_map [B][T][M] (contiguous) or NULL.
+ * dsf_mel_loss_bwd   dx [B][T][M] contiguous = d/dx of grad_out[0] out[0] + grad_out[1] out[1] + grad_out[2] out[2] + sum(grad_map * map)
+ *                    (grad_out a DEVICE [3], grad_map NULL or [B][T][M]); stats = the forward's out.  y gets no gradient.
+ * dsf_dur_loss       add_dur_loss with dur_loss 'mse': out = [pdur, wdur, sdur] (each times its lambda; pass lam_ph = 1 for the MIDI tasks,
+ *                    which do not scale pdur).  dur_pred [B][T_txt] (log domain), txt_tokens [B][T_txt], mel2ph [B][T] int64, T_txt <= 2048.
+ *                    Words: silence-phone ids sil_ids [n_sil] (DEVICE; FastSpeech2Task: word_id = cumsum(is_sil) * (1 - is_sil), word 0
+ *                    dropped) or word_boundary [B][T_txt] (DEVICE int64; the MIDI tasks: idx = pad(cumsum(wdb))[:, :-1], every word kept).  A
+ *                    mel2ph value outside [0, T_txt] (or a word_boundary value outside [0, T_txt], or more words than phones) gives NaN.
+ * dsf_dur_loss_bwd   grad [B][T_txt] = d/d dur_pred of grad_out . out (grad_out a DEVICE [3]). */
+int64_t dsf_fs2_loss_workspace_floats(int32_t B, int32_t T, int32_t which);
+int dsf_mel_loss(const float* x, int64_t x_sb, int64_t x_st, const float* y, int64_t y_sb, int64_t y_st, int32_t B, int32_t T, int32_t M, float bias,
+                 int32_t weighted, int32_t terms, float lam_l1, float lam_ssim, float* ssim_map, float* workspace, float* out, void* stream);
+int dsf_mel_loss_bwd(const float* x, int64_t x_sb, int64_t x_st, const float* y, int64_t y_sb, int64_t y_st, int32_t B, int32_t T, int32_t M, float bias,
+                     int32_t weighted, int32_t terms, float lam_l1, float lam_ssim, const float* stats, const float* grad_out, const float* grad_map,
+                     float* dx, void* stream);
+int dsf_dur_loss(const float* dur_pred, const int64_t* mel2ph, const int64_t* txt_tokens, const int64_t* sil_ids, int32_t n_sil,
+                 const int64_t* word_boundary, int32_t B, int32_t T_txt, int32_t T, float lam_ph, float lam_word, float lam_sent, float* workspace,
+                 float* out, void* stream);
+int dsf_dur_loss_bwd(const float* dur_pred, const int64_t* mel2ph, const int64_t* txt_tokens, const int64_t* sil_ids, int32_t n_sil,
+                     const int64_t* word_boundary, int32_t B, int32_t T_txt, int32_t T, float lam_ph, float lam_word, float lam_sent,
+                     const float* workspace, const float* grad_out, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
