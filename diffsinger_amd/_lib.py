@@ -8,7 +8,7 @@ import os
 
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libdsdenoise.so')
 
-DSD_ABI_VERSION = 7
+DSD_ABI_VERSION = 8
 
 # every symbol include/dsd.h declares (tests check the .so exports exactly these)
 SYMBOLS = [
@@ -29,7 +29,7 @@ SYMBOLS_FS2 = ['dsf_padded_frames', 'dsf_packed_floats', 'dsf_pack_weight', 'dsf
                'dsf_train_add_step', 'dsf_train_rowsum', 'dsf_train_gate', 'dsf_train_gate_bwd', 'dsf_train_res_skip', 'dsf_train_res_skip_bwd',
                'dsf_channel_affine', 'dsf_group_norm', 'dsf_adamw_step',
                'dsf_stack_workspace_floats', 'dsf_set_stack_mode', 'dsf_set_stack_conv', 'dsf_get_stack_conv', 'dsf_set_wgrad_dual', 'dsf_debug_trb_timeline', 'dsf_stack_offsets', 'dsf_stack_forward', 'dsf_stack_backward', 'dsf_wgrad2_workspace_floats', 'dsf_conv1d_wgrad2', 'dsf_wgrad_probe', 'dsf_wgrad_probe_read',
-               'dsf_fs2_loss_workspace_floats', 'dsf_mel_loss', 'dsf_mel_loss_bwd', 'dsf_dur_loss', 'dsf_dur_loss_bwd']
+               'dsf_fs2_loss_workspace_floats', 'dsf_mel_loss', 'dsf_mel_loss_bwd', 'dsf_dur_loss', 'dsf_dur_loss_bwd', 'dsf_length_regulate']
 
 # every symbol include/dsv.h declares (the HiFi-GAN / NSF-HiFi-GAN generator ops)
 SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'dsv_pad_rows', 'dsv_conv1d', 'dsv_conv1d_multi', 'dsv_set_lean', 'dsv_noise_conv', 'dsv_sine_source',
@@ -178,6 +178,7 @@ def load():
     lib.dsf_mel_loss_bwd.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, f32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
     lib.dsf_dur_loss.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp]
     lib.dsf_dur_loss_bwd.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]
+    lib.dsf_length_regulate.argtypes = [vp, vp, f32, vp, f32, vp, vp, vp, i32, i32, i32, vp]
     lib.dsv_padded_samples.argtypes = [i32]
     lib.dsv_padded_samples.restype = i32
     lib.dsv_packed_floats.argtypes = [i32, i32, i32]

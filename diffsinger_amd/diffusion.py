@@ -19,6 +19,7 @@ import torch
 from torch import nn
 
 from .hparams import hparams
+from . import fs2 as _fs2
 from .net import DiffNet
 
 
@@ -59,6 +60,14 @@ def _build_fs2(phone_encoder, out_dims):
         return FastSpeech2(phone_encoder, out_dims)
     except ImportError:
         return None
+
+
+def _check_budget(ret, max_frames):
+    """After the loop's wait: a row whose predicted length exceeds the caller's frame budget was cut - say so, loudly."""
+    need = int(ret['mel_len'].max())
+    if need > max_frames:
+        raise RuntimeError(f'max_frames={max_frames} is too small: the longest row needs {need} frames (ret[\'mel_len\'] = '
+                           f'{ret["mel_len"].tolist()}); call again with max_frames >= {need}')
 
 
 class GaussianDiffusion(nn.Module):
@@ -304,20 +313,29 @@ class GaussianDiffusion(nn.Module):
         return (mel, x) if return_x else mel
 
     def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None, infer=False,
-                **kwargs):
+                max_frames=None, **kwargs):
         """:233-276.  Needs `self.fs2` (the reference's FastSpeech2) for the conditioner; the diffusion loop is
-        `inference()`."""
+        `inference()`.  max_frames (infer=True, mel2ph=None, the HIP FastSpeech2): the frame budget of the free-running forward
+        (fs2.FastSpeech2.forward) - frames past a row's predicted length are 0 in mel_out; a row longer than the budget raises."""
         if self.fs2 is None:
             raise RuntimeError('no FastSpeech2 attached (self.fs2): run inside the reference tree, pass fs2=, or call '
                                'inference(cond, ...) with a precomputed conditioner')
         if not infer:
+            if max_frames is not None:
+                raise ValueError('max_frames belongs to the free-running inference forward (infer=True, mel2ph=None)')
             return self._forward_train(txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, **kwargs)
+        if max_frames is not None:
+            kwargs['max_frames'] = _fs2.check_max_frames(max_frames, mel2ph)
         ret = self.fs2(txt_tokens, mel2ph, spk_embed, ref_mels, f0, uv, energy, skip_decoder=False, infer=True, **kwargs)
         cond = ret['decoder_inp'].transpose(1, 2)
         ret['fs2_mel'] = ret['mel_out']
         mask = (mel2ph > 0).float() if mel2ph is not None else None           # :272-273
+        if max_frames is not None:
+            mask = (ret['mel2ph'] > 0).float()                                 # the budget's tail is padding: the same mask on the predicted mel2ph
         # the caller reads the mel next (tasks/tts/fs2.py:394-431 moves it to the host): waiting here costs nothing and a starved loop is loud
         ret['mel_out'] = self.inference(cond, fs2_mels=ret['mel_out'], mel_mask=mask, check=True)
+        if max_frames is not None:
+            _check_budget(ret, max_frames)
         return ret
 
     def p_losses(self, x_start, t, cond, noise=None, nonpadding=None):
@@ -358,9 +376,13 @@ class OfflineGaussianDiffusion(GaussianDiffusion):
     ref_mels[1] (:306-313), DDPM only (:318-319), `gaussian_start` honoured (:314-317), no `mel2ph > 0` mask on the output."""
 
     def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None, infer=False,
-                **kwargs):
+                max_frames=None, **kwargs):
         if self.fs2 is None:
             raise RuntimeError('no FastSpeech2 attached (self.fs2)')
+        if max_frames is not None:
+            if not infer:
+                raise ValueError('max_frames belongs to the free-running inference forward (infer=True, mel2ph=None)')
+            kwargs['max_frames'] = _fs2.check_max_frames(max_frames, mel2ph)
         # :295-296 passes infer=True in BOTH branches; FastSpeech2.forward does not read the flag (fs2.py:93-149) - the HIP FastSpeech2 takes it as
         # "no autograd graph", so the training branch hands it infer=False to keep the reference's gradient flow into a trainable FastSpeech2
         from .fs2 import FastSpeech2 as HipFS2
@@ -374,5 +396,8 @@ class OfflineGaussianDiffusion(GaussianDiffusion):
             x = self.norm_spec(target).transpose(1, 2)[:, None, :, :]
             ret['diff_loss'] = self.p_losses(x, t, cond)
         else:
-            ret['mel_out'] = self.inference(cond, fs2_mels=fs2_mels, pndm_speedup=0, check=True)
+            mask = (ret['mel2ph'] > 0).float() if max_frames is not None else None
+            ret['mel_out'] = self.inference(cond, fs2_mels=fs2_mels, pndm_speedup=0, mel_mask=mask, check=True)
+            if max_frames is not None:
+                _check_budget(ret, max_frames)
         return ret

@@ -287,6 +287,81 @@ def set_pitch_native(pow: bool = True, log: bool = True):
     _PITCH_NATIVE['pow'], _PITCH_NATIVE['log'] = bool(pow), bool(log)
 
 
+# How much of the free-running duration path runs inside dsf_length_regulate: `regulate` False = the reference's torch op sequence (the mask-and-sum
+# regulator with its host read; the yardstick of tools/bench_free.py), `exp` False = exp / round / clamp from torch's own kernels and the
+# operator on integer durations - for a host whose tensor library's exp rounds differently from this library's (tests/test_gpu_length_regulate.py
+# compares them).  Unlike set_glue this leaves the other glue operators on.
+_REGULATE_NATIVE = {'regulate': True, 'exp': True}
+
+
+def set_regulate_native(regulate: bool = True, exp: bool = True):
+    _REGULATE_NATIVE['regulate'], _REGULATE_NATIVE['exp'] = bool(regulate), bool(exp)
+
+
+def _regulate_ok(*tensors) -> bool:
+    return _REGULATE_NATIVE['regulate'] and _glue_ok(*tensors)
+
+
+def length_regulate_op(*, dur=None, logdur=None, offset=1.0, dur_padding=None, alpha=1.0, frames=None):
+    """dsf_length_regulate: out2dur (logdur form) + LengthRegulator (tts_modules.py:122-131, :158-186) as ONE launch on a frame axis of `frames`
+    -> (dur_choice int64 [B,T_txt] or None (dur form), mel2ph int64 [B,frames], mel_len int32 [B] = the rows' own lengths, not clipped).
+    frames=None: only dur_choice and mel_len (mel2ph is None) - the first launch of a caller that sizes the axis from mel_len."""
+    if (dur is None) == (logdur is None):
+        raise ValueError('length_regulate_op: exactly one of dur and logdur')
+    src = dur if dur is not None else logdur
+    _need_hip(src, 'length_regulate_op')
+    B, Tt = src.shape
+    dev = src.device
+    src = src.contiguous()
+    if src.dtype != (torch.int64 if dur is not None else torch.float32):
+        raise TypeError(f'length_regulate_op: dur must be int64 / logdur float32 (got {src.dtype})')
+    pad = None
+    if dur_padding is not None:
+        pad = dur_padding.contiguous()
+        pad = pad.view(torch.uint8) if pad.dtype == torch.bool else (pad != 0).view(torch.uint8)
+    choice = torch.empty(B, Tt, device=dev, dtype=torch.int64) if logdur is not None else None
+    mel2ph = torch.empty(B, int(frames), device=dev, dtype=torch.int64) if frames is not None else None
+    mel_len = torch.empty(B, device=dev, dtype=torch.int32)
+    p = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().dsf_length_regulate(p(src) if dur is not None else None, p(src) if logdur is not None else None, float(offset), p(pad),
+                                                   float(alpha), p(choice), p(mel2ph), mel_len.data_ptr(), B, Tt,
+                                                   int(frames) if frames is not None else 1, _stream(dev)), 'dsf_length_regulate')
+    return choice, mel2ph, mel_len
+
+
+def frame_keep(mel2ph: torch.Tensor):
+    """Where the frame axis is alive: float [B,T], 1 on the frames up to the last one that ANY row of the batch owns (mel2ph > 0), 0 on the columns
+    behind it, which are padding for every row - what a frame budget (max_frames) or a collated mel2ph with spare columns appends.  Also the
+    number of live frames as a float scalar tensor.  No host read.
+
+    Why it exists: the reference masks nothing between a LayerNorm and the k > 1 convolution behind it (EncSALayer's layer_norm2 -> ffn_1,
+    common_layers.py:565-588; the pitch / energy / cwt predictors' stacks, tts_modules.py:215-229), so a padding frame enters that convolution as
+    the LayerNorm's bias where the END of the tensor enters as zero - a row's mel depends on whether padding frames follow it.  For the shorter
+    rows of a batch that is the reference's arithmetic and stays.  For columns that no row owns it would make the result depend on how long the
+    caller happened to make the axis; multiplying those columns by this mask makes them the end of the tensor: the forward on a budget of N
+    frames computes what the forward on exactly max(mel_len) frames computes.  Where every column is owned (any mel2ph the reference itself
+    builds) the mask is all ones and nothing changes, bit for bit."""
+    B, T = mel2ph.shape
+    ar = torch.arange(1, T + 1, device=mel2ph.device)
+    live = ((mel2ph > 0).any(0) * ar).max()                                   # 1 + the last owned column; 0 for an empty batch
+    keep = (ar <= live).float()
+    return keep[None].expand(B, T).contiguous(), live.float()
+
+
+def check_max_frames(max_frames, mel2ph=None):
+    """The frame budget of a free-running forward, validated on the host before any device work: None, or an int >= 1 and no mel2ph beside it."""
+    if max_frames is None:
+        return None
+    if isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)):
+        raise ValueError(f'max_frames must be an int (got {max_frames!r})')
+    if max_frames < 1:
+        raise ValueError(f'max_frames must be >= 1 (got {max_frames})')
+    if mel2ph is not None:
+        raise ValueError("max_frames sizes the frame axis of the free-running forward (mel2ph=None); with mel2ph given the axis is mel2ph's")
+    return int(max_frames)
+
+
 def _pitch_fusable(f0, uv, hp) -> bool:
     return (_glue_ok(f0, uv) and torch.is_tensor(f0) and f0.dtype == torch.float32 and f0.dim() == 2 and hp['pitch_norm'] in ('standard', 'log')
             and (uv is None or not hp['use_uv'] or (uv.shape == f0.shape and uv.dtype in (torch.float32, torch.bool, torch.uint8))))
@@ -549,8 +624,8 @@ class EncSALayer(nn.Module):
         self.layer_norm2 = nn.LayerNorm(c)
         self.ffn = TransformerFFNLayer(c, 4 * c, kernel_size=kernel_size, padding=padding, act=act)
 
-    def forward_cm(self, x, T, keep, pad_u8):
-        """EncSALayer.forward (common_layers.py:565-588) on a cm tensor; with self.training and dropout > 0 the three dropouts of the reference
+    def forward_cm(self, x, T, keep, pad_u8, col_keep=None):
+        """EncSALayer.forward (common_layers.py:565-588) on a cm tensor; col_keep: see frame_keep (zero where the frame axis has ended for every row); with self.training and dropout > 0 the three dropouts of the reference
         (:576, TransformerFFNLayer :520, :584) sit between the convolutions and their residual adds, so those run unfused."""
         a, f = self.self_attn, self.ffn
         p = self.dropout if self.training else 0.0
@@ -561,7 +636,7 @@ class EncSALayer(nn.Module):
             x = (x + F.dropout(conv1d_cm(o, T, a.out_proj.weight, a._pout), p, True)) * _keep_cm(keep, x.shape[2])
         else:
             x = conv1d_cm(o, T, a.out_proj.weight, a._pout, residual=x, keep=keep)
-        y = layer_norm_cm(x, T, self.layer_norm2.weight, self.layer_norm2.bias, 1e-5)
+        y = layer_norm_cm(x, T, self.layer_norm2.weight, self.layer_norm2.bias, 1e-5, keep=col_keep)
         hdn = conv1d_cm(y, T, f.ffn_1.weight, f._p1, f.ffn_1.bias, scale=f.kernel_size ** -0.5, act=f.act)
         if p > 0:
             out = conv1d_cm(F.dropout(hdn, p, True), T, f.ffn_2.weight, f._p2, f.ffn_2.bias)
@@ -586,8 +661,9 @@ class FFTBlocks(nn.Module):
         self.layers = nn.ModuleList([TransformerEncoderLayer(hidden_size, ffn_kernel_size, num_heads) for _ in range(num_layers)])
         self.layer_norm = nn.LayerNorm(hidden_size) if use_last_norm else None
 
-    def forward_cm(self, x, padding_mask=None):
-        """FFTBlocks.forward (tts_modules.py:288-314), eval mode.  x [B,T,C] -> channel-major [B][C][TS] (and T, keep)."""
+    def forward_cm(self, x, padding_mask=None, col_keep=None):
+        """FFTBlocks.forward (tts_modules.py:288-314), eval mode.  x [B,T,C] -> channel-major [B][C][TS] (and T, keep).  col_keep: frame_keep of
+        a mel-rate stack (the frames past every row's end count as the end of the tensor)."""
         _need_hip(x, 'FFTBlocks')
         T = x.shape[1]
         if _glue_ok(x, padding_mask) and x.dtype == torch.float32 and not (self.use_pos_embed and self.training and hparams['dropout'] > 0):
@@ -598,7 +674,7 @@ class FFTBlocks(nn.Module):
                 pos, tab = positions_op(x=x, padding_idx=self.embed_positions.padding_idx), self.embed_positions.table(T)
             xc, keep, pad_u8 = input_cm_op(x=x, pos=pos, pos_table=tab, alpha=self.pos_embed_alpha if self.use_pos_embed else None,
                                            padding_mask=padding_mask)
-            return self.layers_cm(xc, T, keep, pad_u8)
+            return self.layers_cm(xc, T, keep, pad_u8, col_keep)
         padding_mask = x.abs().sum(-1).eq(0) if padding_mask is None else padding_mask
         keep = (~padding_mask).float().contiguous()
         pad_u8 = padding_mask.to(torch.uint8).contiguous()
@@ -606,11 +682,11 @@ class FFTBlocks(nn.Module):
             x = x + self.pos_embed_alpha * self.embed_positions(x[..., 0])
             x = _drop(x, hparams['dropout'], self.training)                          # tts_modules.py:293
         xc = to_cm(x * keep[:, :, None])
-        return self.layers_cm(xc, T, keep, pad_u8)
+        return self.layers_cm(xc, T, keep, pad_u8, col_keep)
 
-    def layers_cm(self, xc, T, keep, pad_u8):
+    def layers_cm(self, xc, T, keep, pad_u8, col_keep=None):
         for layer in self.layers:
-            xc = layer.op.forward_cm(xc, T, keep, pad_u8)
+            xc = layer.op.forward_cm(xc, T, keep, pad_u8, col_keep)
         if self.layer_norm is not None:
             xc = layer_norm_cm(xc, T, self.layer_norm.weight, self.layer_norm.bias, 1e-5, keep=keep)
         return xc, T, keep
@@ -725,15 +801,22 @@ class DurationPredictor(nn.Module):
         self._packs = [PackedWeight() for _ in range(n_layers)]
         self._plin = PackedWeight()
 
-    def _forward(self, xs, x_masks, is_inference, keep=None):
-        """tts_modules.py:107-120.  xs [B,T,idim]; x_masks [B,T] bool (True = pad); keep: (~x_masks).float() if the caller has it (dsf_token_masks)."""
+    def log_durations(self, xs, x_masks, keep=None):
+        """tts_modules.py:107-118: the predictor's output [B,T,1] (log domain).  xs [B,T,idim]; x_masks [B,T] bool (True = pad); keep:
+        (~x_masks).float() if the caller has it (dsf_token_masks)."""
         T = xs.shape[1]
         keep = (~x_masks).float().contiguous() if keep is None else keep
         xc = _run_pred_convs(self.conv, self._packs, to_cm(xs), T, keep)
-        y = from_cm(conv1d_cm(xc, T, self.linear.weight, self._plin, self.linear.bias, keep=keep), T)        # [B,T,1]
+        return from_cm(conv1d_cm(xc, T, self.linear.weight, self._plin, self.linear.bias, keep=keep), T)
+
+    def out2dur(self, y):
+        """tts_modules.py:122-131 on y [B,T] as torch ops (on the operator path it is part of dsf_length_regulate)."""
+        return torch.clamp(torch.round(y.exp() - self.offset), min=0).long()
+
+    def _forward(self, xs, x_masks, is_inference, keep=None):
+        y = self.log_durations(xs, x_masks, keep)                                                           # [B,T,1]
         if is_inference:
-            dur = torch.clamp(torch.round(y.squeeze(-1).exp() - self.offset), min=0).long()                 # out2dur :122-131
-            return dur, y
+            return self.out2dur(y.squeeze(-1)), y
         return y.squeeze(-1)
 
     def forward(self, xs, x_masks=None, keep=None):
@@ -742,19 +825,49 @@ class DurationPredictor(nn.Module):
     def inference(self, xs, x_masks=None, keep=None):
         return self._forward(xs, x_masks, True, keep)
 
+    def regulate(self, xs, x_masks, regulator, keep=None, max_frames=None):
+        """inference() followed by the length regulator -> (dur_choice, log-durations [B,T,1], mel2ph, mel_len int32 [B]).  On the operator path
+        out2dur and the regulator are ONE launch (dsf_length_regulate, logdur form); set_regulate_native(exp=False) takes out2dur from torch."""
+        y = self.log_durations(xs, x_masks, keep)
+        logdur = y.squeeze(-1)
+        if _regulate_ok(logdur, x_masks) and _REGULATE_NATIVE['exp'] and logdur.dtype == torch.float32:
+            if max_frames is not None:
+                dur, mel2ph, mel_len = length_regulate_op(logdur=logdur, offset=self.offset, dur_padding=x_masks, frames=max_frames)
+                return dur, y, mel2ph, mel_len
+            dur, _, mel_len = length_regulate_op(logdur=logdur, offset=self.offset, dur_padding=x_masks)
+            return (dur, y) + regulator.regulate(dur, x_masks, mel_len=mel_len)
+        dur = self.out2dur(logdur)
+        return (dur, y) + regulator.regulate(dur, x_masks, max_frames=max_frames)
+
 
 class LengthRegulator(nn.Module):
-    def forward(self, dur, dur_padding=None, alpha=1.0):
-        """tts_modules.py:158-186 (index arithmetic only)."""
+    def forward(self, dur, dur_padding=None, alpha=1.0, max_frames=None):
+        """tts_modules.py:158-186 (index arithmetic only) -> mel2ph [B, T_mel].  max_frames=None: T_mel = the longest row (one read of it on the
+        host, as in the reference).  max_frames=N: T_mel = N with no host read; rows longer than N are cut at N, shorter ones end in 0."""
+        return self.regulate(dur, dur_padding, alpha, check_max_frames(max_frames))[0]
+
+    def regulate(self, dur, dur_padding=None, alpha=1.0, max_frames=None, mel_len=None):
+        """-> (mel2ph, mel_len int32 [B]: the rows' own lengths, not clipped to max_frames).  mel_len: the lengths if the caller has them already
+        (dsf_length_regulate's first launch); they size the axis and spare that launch."""
+        if _regulate_ok(dur, dur_padding) and dur.dim() == 2 and dur.dtype == torch.int64:
+            if max_frames is None:
+                if mel_len is None:
+                    mel_len = length_regulate_op(dur=dur, dur_padding=dur_padding, alpha=alpha)[2]
+                max_frames = int(mel_len.max())
+                if max_frames == 0:
+                    return torch.zeros(dur.shape[0], 0, device=dur.device, dtype=torch.int64), mel_len
+            _, mel2ph, mel_len = length_regulate_op(dur=dur, dur_padding=dur_padding, alpha=alpha, frames=max_frames)
+            return mel2ph, mel_len
         dur = torch.round(dur.float() * alpha).long()
         if dur_padding is not None:
             dur = dur * (1 - dur_padding.long())
         token_idx = torch.arange(1, dur.shape[1] + 1)[None, :, None].to(dur.device)
         dur_cumsum = torch.cumsum(dur, 1)
         dur_cumsum_prev = F.pad(dur_cumsum, [1, -1], mode='constant', value=0)
-        pos_idx = torch.arange(int(dur.sum(-1).max()))[None, None].to(dur.device)
+        lens = dur.sum(-1)
+        pos_idx = torch.arange(int(lens.max()) if max_frames is None else max_frames)[None, None].to(dur.device)
         token_mask = (pos_idx >= dur_cumsum_prev[:, :, None]) & (pos_idx < dur_cumsum[:, :, None])
-        return (token_idx * token_mask.long()).sum(1)
+        return (token_idx * token_mask.long()).sum(1), lens.to(torch.int32)
 
 
 class PitchPredictor(nn.Module):
@@ -768,17 +881,18 @@ class PitchPredictor(nn.Module):
         self._packs = [PackedWeight() for _ in range(n_layers)]
         self._plin = PackedWeight()
 
-    def forward(self, xs):
-        """tts_modules.py:215-229.  xs [B,T,idim] -> [B,T,odim]."""
+    def forward(self, xs, keep=None):
+        """tts_modules.py:215-229.  xs [B,T,idim] -> [B,T,odim].  keep: frame_keep of a mel-rate input (None: the reference's unmasked stack)."""
         T = xs.shape[1]
         if _glue_ok(xs) and xs.dtype == torch.float32 and xs.shape[2] % 4 == 0:
             xs = xs.contiguous()                                   # positions + positional embedding + transposition: two launches
+            # keep: the stack's input ends where the frame axis ends too (the cwt predictor's input is a Linear's output: its bias on every column)
             xc0, _, _ = input_cm_op(x=xs, pos=positions_op(x=xs, padding_idx=self.embed_positions.padding_idx), pos_table=self.embed_positions.table(T),
-                                    alpha=self.pos_embed_alpha, mask=False)
+                                    alpha=self.pos_embed_alpha, padding_mask=(keep == 0) if keep is not None else None, mask=keep is not None)
         else:
             xs = xs + self.pos_embed_alpha * self.embed_positions(xs[..., 0])
-            xc0 = to_cm(xs)
-        xc = _run_pred_convs(self.conv, self._packs, xc0, T, None)
+            xc0 = to_cm(xs if keep is None else xs * keep[:, :, None])
+        xc = _run_pred_convs(self.conv, self._packs, xc0, T, keep)
         return from_cm(conv1d_cm(xc, T, self.linear.weight, self._plin, self.linear.bias), T)
 
 
@@ -901,17 +1015,21 @@ class FastSpeech2(nn.Module):
         return self.encoder(txt_tokens)
 
     def forward(self, txt_tokens, mel2ph=None, spk_embed=None, ref_mels=None, f0=None, uv=None, energy=None, skip_decoder=False,
-                spk_embed_dur_id=None, spk_embed_f0_id=None, infer=False, **kwargs):
+                spk_embed_dur_id=None, spk_embed_f0_id=None, infer=False, max_frames=None, **kwargs):
         """fs2.py:93-149.  infer=True (or torch.no_grad()): the inference kernels with their fused epilogues.  infer=False with autograd on:
         the same forward as an autograd graph whose backward runs on HIP kernels too (the operator layer above) - what DiffSingerTask /
         DiffSingerMIDITask train when `fs2_ckpt` is empty (usr/diffsinger_task.py:60-64, :273-300); the gradient scaling of the predictor
-        inputs (`predictor_grad`, fs2.py:153, :194) is part of the graph."""
+        inputs (`predictor_grad`, fs2.py:153, :194) is part of the graph.
+        max_frames (free-running mode only: mel2ph=None): the length of the frame axis, chosen by the caller instead of read back from the predicted
+        durations - no host synchronisation in the forward, so it is capturable (graphs.GraphedForward).  Frames past a row's length are
+        padding frames (mel2ph == 0), a row longer than the budget is cut: ret['mel_len'] (int32 [B], not clipped) says so."""
+        max_frames = check_max_frames(max_frames, mel2ph)
         if infer or not torch.is_grad_enabled():
             with torch.no_grad():
                 return self._forward(txt_tokens, mel2ph, f0, uv, skip_decoder, infer, spk_embed=spk_embed, energy=energy,
-                                     spk_embed_dur_id=spk_embed_dur_id, spk_embed_f0_id=spk_embed_f0_id, **kwargs)
+                                     spk_embed_dur_id=spk_embed_dur_id, spk_embed_f0_id=spk_embed_f0_id, max_frames=max_frames, **kwargs)
         return self._forward(txt_tokens, mel2ph, f0, uv, skip_decoder, infer, spk_embed=spk_embed, energy=energy,
-                             spk_embed_dur_id=spk_embed_dur_id, spk_embed_f0_id=spk_embed_f0_id, **kwargs)
+                             spk_embed_dur_id=spk_embed_dur_id, spk_embed_f0_id=spk_embed_f0_id, max_frames=max_frames, **kwargs)
 
     def _speaker(self, spk_embed, spk_embed_dur_id, spk_embed_f0_id):
         """fs2.py:107-121 -> (spk_embed_dur, spk_embed_f0, spk_embed), each [B,1,H] or 0."""
@@ -928,7 +1046,7 @@ class FastSpeech2(nn.Module):
         return 0, 0, 0
 
     def _forward(self, txt_tokens, mel2ph, f0, uv, skip_decoder, infer, spk_embed=None, energy=None, spk_embed_dur_id=None,
-                 spk_embed_f0_id=None, **kwargs):
+                 spk_embed_f0_id=None, max_frames=None, **kwargs):
         ret = {}
         encoder_out = self._encode(txt_tokens, **kwargs)                                        # [B,T_txt,H]
         spk_dur, spk_f0, spk = self._speaker(spk_embed, spk_embed_dur_id, spk_embed_f0_id)
@@ -941,17 +1059,18 @@ class FastSpeech2(nn.Module):
             src_nonpadding = src_np[:, :, None]
             masked_enc = lambda s_: sum_embed_op(enc_c, tok_c, spk=s_ if torch.is_tensor(s_) else None)
             dur_inp = masked_enc(spk_dur)
-            mel2ph = self.add_dur(dur_inp, mel2ph, txt_tokens, ret, src_padding=src_padding, keep=src_keep)
+            mel2ph = self.add_dur(dur_inp, mel2ph, txt_tokens, ret, src_padding=src_padding, keep=src_keep, max_frames=max_frames)
         else:
             src_nonpadding = (txt_tokens > 0).float()[:, :, None]
             dur_inp = (encoder_out + spk_dur) * src_nonpadding
-            mel2ph = self.add_dur(dur_inp, mel2ph, txt_tokens, ret)
+            mel2ph = self.add_dur(dur_inp, mel2ph, txt_tokens, ret, max_frames=max_frames)
         if glue and _glue_ok(mel2ph) and mel2ph.dtype == torch.int64:
             # fs2.py:128-141 as two launches: the length regulator's gather (+ the predictors' masked input), then every embedding, the speaker
             # embedding and the mask in one pass over [B,T,H] (the pad / repeat / gather / add / mul sequence of the reference moved ~100 MB)
             m2p = mel2ph.contiguous()
             tgt_np, tgt_padding, _ = token_masks_op(m2p, gt0=True, eq0=True)
             tgt_nonpadding = tgt_np[:, :, None]
+            fk = frame_keep(m2p) if not torch.is_grad_enabled() else None
             decoder_inp, pitch_inp = gather_frames_op(enc_c, m2p, spk_f0)
             idx1 = tab1 = idx2 = tab2 = None
             if hparams['use_pitch_embed']:
@@ -959,27 +1078,28 @@ class FastSpeech2(nn.Module):
                 enc_f0 = None
                 if hparams['pitch_type'] in ('ph', 'cwt'):
                     enc_f0 = dur_inp if (not torch.is_tensor(spk_f0) and not torch.is_tensor(spk_dur)) else masked_enc(spk_f0)
-                idx1 = self.add_pitch(pitch_inp, f0, uv, m2p, ret, encoder_out=enc_f0, want_index=True, pitch_padding=tgt_padding).contiguous()
+                idx1 = self.add_pitch(pitch_inp, f0, uv, m2p, ret, encoder_out=enc_f0, want_index=True, pitch_padding=tgt_padding, fk=fk).contiguous()
                 tab1 = self.pitch_embed.weight
             if hparams.get('use_energy_embed'):
-                idx2, tab2 = self.add_energy(pitch_inp, energy, ret, want_index=True).contiguous(), self.energy_embed.weight
+                idx2, tab2 = self.add_energy(pitch_inp, energy, ret, want_index=True, fk=fk).contiguous(), self.energy_embed.weight
             ret['decoder_inp'] = decoder_inp = sum_embed_op(decoder_inp, m2p, idx1=idx1, tab1=tab1, idx2=idx2, tab2=tab2, spk=spk)
             if skip_decoder:
                 return ret
-            ret['mel_out'] = self.run_decoder(decoder_inp, tgt_nonpadding, ret, infer=infer, **kwargs)
+            ret['mel_out'] = self.run_decoder(decoder_inp, tgt_nonpadding, ret, infer=infer, fk=fk, **kwargs)
             return ret
         tgt_nonpadding = (mel2ph > 0).float()[:, :, None]
+        fk = frame_keep(mel2ph) if not torch.is_grad_enabled() else None
         decoder_inp = F.pad(encoder_out, [0, 0, 1, 0])
         decoder_inp = torch.gather(decoder_inp, 1, mel2ph[..., None].repeat([1, 1, encoder_out.shape[-1]]))
         pitch_inp = (decoder_inp + spk_f0) * tgt_nonpadding
         if hparams['use_pitch_embed']:
-            decoder_inp = decoder_inp + self.add_pitch(pitch_inp, f0, uv, mel2ph, ret, encoder_out=(encoder_out + spk_f0) * src_nonpadding)
+            decoder_inp = decoder_inp + self.add_pitch(pitch_inp, f0, uv, mel2ph, ret, encoder_out=(encoder_out + spk_f0) * src_nonpadding, fk=fk)
         if hparams.get('use_energy_embed'):
-            decoder_inp = decoder_inp + self.add_energy(pitch_inp, energy, ret)
+            decoder_inp = decoder_inp + self.add_energy(pitch_inp, energy, ret, fk=fk)
         ret['decoder_inp'] = decoder_inp = (decoder_inp + spk) * tgt_nonpadding
         if skip_decoder:
             return ret
-        ret['mel_out'] = self.run_decoder(decoder_inp, tgt_nonpadding, ret, infer=infer, **kwargs)
+        ret['mel_out'] = self.run_decoder(decoder_inp, tgt_nonpadding, ret, infer=infer, fk=fk, **kwargs)
         return ret
 
     @staticmethod
@@ -989,30 +1109,34 @@ class FastSpeech2(nn.Module):
             return x
         return x.detach() + hparams['predictor_grad'] * (x - x.detach())
 
-    def add_dur(self, dur_input, mel2ph, txt_tokens, ret, src_padding=None, keep=None):
-        """fs2.py:151-172.  src_padding / keep: `txt_tokens == 0` and its float complement if the caller has them (dsf_token_masks)."""
+    def add_dur(self, dur_input, mel2ph, txt_tokens, ret, src_padding=None, keep=None, max_frames=None):
+        """fs2.py:151-172.  src_padding / keep: `txt_tokens == 0` and its float complement if the caller has them (dsf_token_masks).  Free-running
+        (mel2ph None): ret['mel_len'] = the rows' predicted lengths (int32 [B], on the device); max_frames sizes the frame axis."""
         src_padding = (txt_tokens == 0) if src_padding is None else src_padding
         dur_input = self._scale_grad(dur_input)
         if mel2ph is None:
-            dur, xs = self.dur_predictor.inference(dur_input, src_padding, keep=keep)
+            dur, xs, mel2ph, ret['mel_len'] = self.dur_predictor.regulate(dur_input, src_padding, self.length_regulator, keep=keep, max_frames=max_frames)
             ret['dur'], ret['dur_choice'] = xs, dur
-            mel2ph = self.length_regulator(dur, src_padding).detach()
+            mel2ph = mel2ph.detach()
         else:
             ret['dur'] = self.dur_predictor(dur_input, src_padding, keep=keep)
         ret['mel2ph'] = mel2ph
         return mel2ph
 
-    def add_energy(self, decoder_inp, energy, ret, want_index=False):
-        """fs2.py:174-181.  want_index: the rows of energy_embed instead of the embedding (the fused glue of _forward looks them up itself)."""
+    def add_energy(self, decoder_inp, energy, ret, want_index=False, fk=None):
+        """fs2.py:174-181.  want_index: the rows of energy_embed instead of the embedding (the fused glue of _forward looks them up itself).
+        fk: frame_keep(mel2ph) (inference)."""
         decoder_inp = self._scale_grad(decoder_inp)
-        ret['energy_pred'] = energy_pred = self.energy_predictor(decoder_inp)[:, :, 0]
+        ret['energy_pred'] = energy_pred = self.energy_predictor(decoder_inp, keep=fk[0] if fk is not None else None)[:, :, 0]
         if energy is None:
             energy = energy_pred
         energy = torch.clamp(energy * 256 // 4, max=255).long()
         return energy if want_index else self.energy_embed(energy)
 
-    def add_pitch(self, decoder_inp, f0, uv, mel2ph, ret, encoder_out=None, want_index=False, pitch_padding=None):
-        """fs2.py:183-231.  want_index: the rows of pitch_embed instead of the embedding; pitch_padding: `mel2ph == 0` if the caller has it."""
+    def add_pitch(self, decoder_inp, f0, uv, mel2ph, ret, encoder_out=None, want_index=False, pitch_padding=None, fk=None):
+        """fs2.py:183-231.  want_index: the rows of pitch_embed instead of the embedding; pitch_padding: `mel2ph == 0` if the caller has it;
+        fk: frame_keep(mel2ph) (inference) for the frame-rate predictors and the cwt statistics."""
+        keep = fk[0] if fk is not None else None
         if hparams['pitch_type'] == 'ph':                                # :184-196: predicted and quantised per phone, gathered to the frames
             pitch_pred_inp = self._scale_grad(encoder_out)
             pitch_padding = encoder_out.sum().abs() == 0
@@ -1029,7 +1153,7 @@ class FastSpeech2(nn.Module):
         given = f0 is not None
         if hparams['pitch_type'] == 'cwt':
             pitch_padding, have_padding = None, False
-            ret['cwt'] = cwt_out = self.cwt_predictor[1](self.cwt_predictor[0](decoder_inp))
+            ret['cwt'] = cwt_out = self.cwt_predictor[1](self.cwt_predictor[0](decoder_inp), keep=keep)
             s = encoder_out[:, 0, :]
             st = self.cwt_stats_layers
             stats_out = _hip_mlp(s, ((st[0], 'relu'), (st[2], 'relu'), (st[4], 'none')))
@@ -1037,11 +1161,11 @@ class FastSpeech2(nn.Module):
             std = ret['f0_std'] = stats_out[:, 1]
             if f0 is None:
                 std = std * hparams['cwt_std_scale']
-                f0 = self.cwt2f0_norm(cwt_out[:, :, :10], mean, std, mel2ph)
+                f0 = self.cwt2f0_norm(cwt_out[:, :, :10], mean, std, mel2ph, fk=fk)
                 if hparams['use_uv']:
                     uv = cwt_out[:, :, -1] > 0
         else:
-            ret['pitch_pred'] = pitch_pred = self.pitch_predictor(decoder_inp)
+            ret['pitch_pred'] = pitch_pred = self.pitch_predictor(decoder_inp, keep=keep)
             if f0 is None:
                 f0 = pitch_pred[:, :, 0]
             if hparams['use_uv'] and uv is None:
@@ -1056,14 +1180,24 @@ class FastSpeech2(nn.Module):
             f0[pitch_padding] = 0           # the reference's in-place edit of the pitch_pred view (:225-226)
         return pitch if want_index else self.pitch_embed(pitch)
 
-    def run_decoder(self, decoder_inp, tgt_nonpadding, ret, infer, **kwargs):
-        xc, T, keep = self.decoder.forward_cm(decoder_inp)                                      # fs2.py:233-237
+    def run_decoder(self, decoder_inp, tgt_nonpadding, ret, infer, fk=None, **kwargs):
+        xc, T, keep = self.decoder.forward_cm(decoder_inp, col_keep=fk[0] if fk is not None else None)                                      # fs2.py:233-237
         return from_cm(conv1d_cm(xc, T, self.mel_out.weight, self._pmel, self.mel_out.bias, keep=tgt_nonpadding[:, :, 0].contiguous()), T)
 
-    def cwt2f0_norm(self, cwt_spec, mean, std, mel2ph):
+    def cwt2f0_norm(self, cwt_spec, mean, std, mel2ph, fk=None):
         b = (torch.arange(0, 10, device=cwt_spec.device).float()[None, None, :] + 1 + 2.5) ** (-2.5)     # utils/cwt.py:118-125
         rec = (cwt_spec * b).sum(-1)
-        rec = (rec - rec.mean(-1, keepdim=True)) / rec.std(-1, keepdim=True)
+        full = (rec - rec.mean(-1, keepdim=True)) / rec.std(-1, keepdim=True)
+        if fk is None:
+            rec = full
+        else:
+            # the same statistics (mean, unbiased standard deviation) over the live frames only (frame_keep); selected on the device, so that an
+            # axis without spare columns keeps the bits of torch's own mean / std
+            keep, live = fk
+            mu = (rec * keep).sum(-1, keepdim=True) / live
+            dev = (rec - mu) * keep
+            masked = (rec - mu) / ((dev * dev).sum(-1, keepdim=True) / (live - 1)).sqrt()
+            rec = torch.where(live == rec.shape[1], full, masked)
         f0 = (rec * std[:, None] + mean[:, None]).exp()
         f0 = torch.cat([f0] + [f0[:, -1:]] * (mel2ph.shape[1] - f0.shape[1]), 1)
         return norm_f0(f0, None, hparams)

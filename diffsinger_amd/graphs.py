@@ -8,8 +8,8 @@ private memory pool and afterwards copies the inputs into the graph's static buf
 memory pool, capture); every captured node is one of this package's HIP kernels or a torch copy.
 
 Limits (checked, loud): tensor arguments only (plus None / python scalars, which become part of the signature); no data-dependent
-shapes inside `fn` (FastSpeech2 in free-running mode sizes the mel axis from predicted durations -> host sync -> not capturable: pass
-`mel2ph`); results are STATIC tensors, valid until the next call with the same signature (clone what must survive)."""
+shapes inside `fn` (FastSpeech2 in free-running mode with max_frames=None sizes the mel axis from predicted durations -> host sync -> not
+capturable: pass `max_frames=N`, which fixes the axis and becomes part of the signature - one graph per distinct budget - or `mel2ph`); results are STATIC tensors, valid until the next call with the same signature (clone what must survive)."""
 from __future__ import annotations
 
 from collections import OrderedDict

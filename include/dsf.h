@@ -302,6 +302,30 @@ int dsf_dur_loss_bwd(const float* dur_pred, const int64_t* mel2ph, const int64_t
                      const int64_t* word_boundary, int32_t B, int32_t T_txt, int32_t T, float lam_ph, float lam_word, float lam_sent,
                      const float* workspace, const float* grad_out, float* grad, void* stream);
 
+/* The length regulator of the free-running forward (fs2.py:151-172 with mel2ph=None) as ONE launch, with the frame axis sized by the CALLER:
+ * no [B][T_txt][T_mel] mask, no read of the predicted length on the host, so the forward is capturable as a graph.
+ * dsf_length_regulate   exactly one of dur [B][T_txt] (int64 durations, LengthRegulator's input) and logdur [B][T_txt] (fp32, the duration
+ *                       predictor's output) is given.  With logdur, first DurationPredictor.out2dur (tts_modules.py:122-131, 'mse'):
+ *                           d = max(rint(expf(y) - offset), 0), each operation once in fp32, half to even     -> dur_out [B][T_txt] (optional;
+ *                           ret['dur_choice']; written in the logdur form only)
+ *                       then LengthRegulator.forward (tts_modules.py:158-186):
+ *                           d = (int64) rintf((float) d * alpha);   d = 0 where dur_padding [B][T_txt] (u8 / bool, optional) is nonzero
+ *                           mel2ph[b][t] = j + 1 for the first token j with cumsum(d[b])[j] > t, 0 where t >= sum(d[b]), t < T_out
+ *                           (the reference's mask-and-sum has one term per frame at most: tokens of length 0 own no frame) -> mel2ph [B][T_out]
+ *                           mel_len[b] = sum(d[b]), NOT clipped to T_out: a caller sees that its budget was too small    -> mel_len [B] (optional)
+ *                       mel2ph may be NULL (only dur_out / mel_len are written: the first of two launches of a caller that wants the exact
+ *                       length); one output at least.  Rows longer than T_out are cut at T_out.
+ *                       Robustness: a NaN log-duration counts as 0; a token's duration saturates at 1 << 20 frames (before and after
+ *                       alpha; dur_out holds the saturated value) and the row sum at INT32_MAX, so +inf or 100.0 as a log-duration give a
+ *                       long row, not a fault (the reference would try to allocate that tensor).  Negative integer durations violate the
+ *                       reference's precondition too and are clamped to 0.
+ *                       Refused (DSD_ERR_INVALID): both or neither of dur / logdur; alpha not positive and finite; B outside [1, 65535];
+ *                       T_txt < 1 or above DSF_REGULATE_MAX_TXT (a row's running sums live in one workgroup's LDS: 4096 int32 = 16 KiB, far
+ *                       above any phone sequence); T_out outside [1, 2^30]; no output. */
+#define DSF_REGULATE_MAX_TXT 4096
+int dsf_length_regulate(const int64_t* dur, const float* logdur, float offset, const uint8_t* dur_padding, float alpha, int64_t* dur_out,
+                        int64_t* mel2ph, int32_t* mel_len, int32_t B, int32_t T_txt, int32_t T_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
