@@ -34,7 +34,9 @@ SYMBOLS_FS2 = ['dsf_padded_frames', 'dsf_packed_floats', 'dsf_pack_weight', 'dsf
 # every symbol include/dsv.h declares (the HiFi-GAN / NSF-HiFi-GAN generator ops)
 SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'dsv_pad_rows', 'dsv_conv1d', 'dsv_conv1d_multi', 'dsv_set_lean', 'dsv_noise_conv', 'dsv_sine_source',
                'dsv_fold_factor', 'dsv_set_fold', 'dsv_conv1d_folded', 'dsv_chain_fold', 'dsv_chain_supported', 'dsv_resblock_chain', 'dsv_resblock_chain_multi', 'dsv_resblock_chain_sum', 'dsv_set_chain_variant', 'dsv_debug_chain_timeline',
-               'dsv_pwg_first', 'dsv_pwg_upsample', 'dsv_pwg_layer']
+               'dsv_pwg_first', 'dsv_pwg_upsample', 'dsv_pwg_layer',
+               'dsv_stft_basis_floats', 'dsv_stft_make_basis', 'dsv_stft_frames', 'dsv_stft', 'dsv_istft_samples', 'dsv_istft_workspace_floats', 'dsv_istft',
+               'dsv_logmel']
 
 _fp = C.POINTER(C.c_float)
 _fpp = C.POINTER(C.c_void_p)
@@ -206,6 +208,18 @@ def load():
     lib.dsv_pwg_first.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.dsv_pwg_upsample.argtypes = [vp, vp, vp, i64, i32, i32, vp]
     lib.dsv_pwg_layer.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.dsv_stft_basis_floats.argtypes = [i32, i32]
+    lib.dsv_stft_basis_floats.restype = i64
+    lib.dsv_stft_make_basis.argtypes = [i32, i32, vp, vp, vp]
+    lib.dsv_stft_frames.argtypes = [i64, i32, i32, i32, i32]
+    lib.dsv_stft_frames.restype = i64
+    lib.dsv_stft.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]
+    lib.dsv_istft_samples.argtypes = [i64, i32, i32, i32]
+    lib.dsv_istft_samples.restype = i64
+    lib.dsv_istft_workspace_floats.argtypes = [i32, i64, i32]
+    lib.dsv_istft_workspace_floats.restype = i64
+    lib.dsv_istft.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.dsv_logmel.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('dsd_abi_version',):

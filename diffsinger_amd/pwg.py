@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .vocoder import _HipOps, padded_samples, register_vocoder
+from .vocoder import _HipOps, _wav2spec, _wav2spec_batch, padded_samples, register_vocoder
 
 
 class _WN(nn.Module):
@@ -271,7 +271,12 @@ def load_pwg_model(config_path, checkpoint_path, stats_path=None, device=None):
 @register_vocoder
 class PWG:
     """vocoders/pwg.py:54-117.  PWG() discovers the checkpoint like the reference (hparams['vocoder_ckpt'], '' = ./wavegan_pretrained);
-    PWG(model, config, scaler, device) wraps a loaded generator.  spec2wav(mel [T,80], f0=[T]) -> wav [T * hop] (numpy)."""
+    PWG(model, config, scaler, device) wraps a loaded generator.  spec2wav(mel [T,80], f0=[T]) -> wav [T * hop] (numpy).
+    wav2spec(wav, return_linear=False) (vocoders/pwg.py:105-122) runs the log10-mel analysis on the device (diffsinger_amd.stft.wav2spec);
+    wav2spec_batch is its device-resident form.  wav2mfcc (:124-137, librosa.feature.mfcc + deltas) is absent."""
+
+    wav2spec = staticmethod(_wav2spec)
+    wav2spec_batch = staticmethod(_wav2spec_batch)
 
     def __init__(self, model: Optional[ParallelWaveGANGenerator] = None, config: Optional[dict] = None, scaler=None, device='cuda'):
         if model is None:

@@ -761,11 +761,37 @@ def denoise(wav: np.ndarray, v: float = 0.1, *, fft_size: int, hop_size: int, wi
     return out[n_fft // 2:len(out) - n_fft // 2]
 
 
+_DENOISE_NATIVE = {'on': True}
+
+
+def set_denoise_native(on: bool = True):
+    """Process-wide A/B switch of HifiGAN.spec2wav's post-filter (hparams['vocoder_denoise_c'] > 0): True (default) = diffsinger_amd.stft.denoise_op
+    on the generator's device output, one device->host copy at the end; False = the host function `denoise` above on the copied waveform."""
+    _DENOISE_NATIVE['on'] = bool(on)
+
+
+def _wav2spec(wav_fn, return_linear=False):
+    """vocoders/pwg.py:105-122 (PWG.wav2spec, inherited by the reference's HifiGAN): see diffsinger_amd.stft.wav2spec."""
+    from .stft import wav2spec
+    return wav2spec(wav_fn, return_linear=return_linear)
+
+
+def _wav2spec_batch(wavs_dev, lengths=None):
+    """Device-resident wav2spec: see diffsinger_amd.stft.wav2spec_batch."""
+    from .stft import wav2spec_batch
+    return wav2spec_batch(wavs_dev, lengths=lengths)
+
+
 @register_vocoder
 class HifiGAN:
     """vocoders/hifigan.py:40-69.  HifiGAN() discovers the checkpoint like the reference does (hparams['vocoder_ckpt']: config.yaml +
     newest model_ckpt_steps_*.ckpt, else config.json + generator_v1) and reads hparams['use_nsf']; HifiGAN(model, device, use_nsf)
-    wraps a generator that is already loaded.  spec2wav(mel [T,80], f0=[T]) -> wav [T*hop] as a numpy array."""
+    wraps a generator that is already loaded.  spec2wav(mel [T,80], f0=[T]) -> wav [T*hop] as a numpy array.
+    wav2spec(wav, return_linear=False) is the reference's static method (log10-mel analysis on the device); wav2spec_batch its
+    device-resident form.  wav2mfcc (librosa.feature.mfcc + deltas) is absent."""
+
+    wav2spec = staticmethod(_wav2spec)
+    wav2spec_batch = staticmethod(_wav2spec_batch)
 
     def __init__(self, model: Optional[HifiGanGenerator] = None, device=None, use_nsf: Optional[bool] = None):
         from .hparams import hparams
@@ -808,6 +834,11 @@ class HifiGAN:
                 y = self.model(c, f0).view(-1)
             else:
                 y = self.model(c).view(-1)
+            if hparams.get('vocoder_denoise_c', 0.0) > 0 and _DENOISE_NATIVE['on']:   # the post-filter on the device, BEFORE the one copy
+                from .stft import denoise_op
+                y = denoise_op(y.view(1, -1), hparams['vocoder_denoise_c'], fft_size=hparams['fft_size'], hop_size=hparams['hop_size'],
+                               win_size=hparams['win_size']).view(-1)
+                return y.cpu().numpy()
         wav_out = y.cpu().numpy()
         if hparams.get('vocoder_denoise_c', 0.0) > 0:                       # vocoders/hifigan.py:63-64
             wav_out = denoise(wav_out, v=hparams['vocoder_denoise_c'], fft_size=hparams['fft_size'], hop_size=hparams['hop_size'],

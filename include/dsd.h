@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-/* 8: dsf_length_regulate.  7: dsf_mel_loss / dsf_mel_loss_bwd / dsf_dur_loss / dsf_dur_loss_bwd / dsf_fs2_loss_workspace_floats.
+/* 8: dsf_length_regulate; later, without a bump (symbols were only ADDED - a caller built against 8 finds everything it knew unchanged): the STFT
+ * family of dsv.h (dsv_stft_basis_floats / dsv_stft_make_basis / dsv_stft_frames / dsv_stft / dsv_istft_samples / dsv_istft_workspace_floats /
+ * dsv_istft / dsv_logmel).  7: dsf_mel_loss / dsf_mel_loss_bwd / dsf_dur_loss / dsf_dur_loss_bwd / dsf_fs2_loss_workspace_floats.
  * 6 (round 6): dsd_get_conv_mode also reports the Winograd conv node of the latency kernels; dsv_set_chain_variant; dsv_resblock_chain refuses
  * sum_in == out; dsf_positions / dsf_input_cm / dsf_gather_frames / dsf_sum_embed / dsf_token_masks / dsf_pitch_coarse / dsf_q_sample_rows / dsf_l1_mean / dsf_l1_mean_bwd; dsf_set_wgrad_dual; dsv_resblock_chain_multi / dsv_resblock_chain_sum / dsv_conv1d_multi / dsv_set_lean.  5 (round 5): dsd_set_conv_mode. */
 #define DSD_ABI_VERSION 8

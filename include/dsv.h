@@ -172,6 +172,66 @@ int dsv_pwg_upsample(const float* in, const float* filter, float* out, int64_t r
 int dsv_pwg_layer(const float* x, const float* c, const float* w1_packed, const float* b1, const float* w2_packed, const float* b2, float* x_out,
                   float* skip, int32_t B, int32_t L, int32_t n_aux, int32_t dil, int32_t first, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * STFT: framed real DFT, its inverse with overlap-add, the spectral-subtraction post-filter and the log-mel analysis (csrc/voc_stft.hpp) -
+ * the other half of the vocoder interface (vocoders/base_vocoder.py:22-39: spec2wav AND wav2spec).  Waveforms are plain [B][L] rows here
+ * (no LS padding).  The DFT is a matrix product on the fp32 MFMA against a precomputed basis with the window folded in; every sum runs in a
+ * fixed order (two calls are bitwise equal), nothing allocates or synchronises.
+ *
+ * Supported: n_fft in {256, 512, 1024, 2048}, 1 <= win_length <= n_fft (periodic Hann window centred in the frame, zero outside - scipy's
+ * get_window('hann', win_length) through librosa.util.pad_center), 1 <= hop <= n_fft, B <= 65535, L <= 2^30.  Everything else is refused with
+ * DSD_ERR_INVALID before any launch.
+ *
+ * Bases: dsv_stft_basis_floats(n_fft, which) floats each (-1: unsupported n_fft); dsv_stft_make_basis fills either or both ON THE DEVICE in
+ * float64 (angles reduced exactly, each entry the float32 rounding of the float64 value) - one launch, once per (n_fft, win_length); call it
+ * outside a graph capture and keep the buffers.  DSV_STFT_BASIS_FWD carries the analysis window; DSV_STFT_BASIS_INV the synthesis window,
+ * 1 / n_fft, the factor 2 of the interior bins, and behind them float32(w[n]^2) for the window sum-of-squares.
+ *
+ * Framing: pad_l / pad_r samples of padding per side applied by index arithmetic (DSV_STFT_PAD_CONSTANT: zeros, librosa.stft(pad_mode=
+ * 'constant'), data_gen/tts/data_gen_utils.py:123-124; DSV_STFT_PAD_REFLECT: torch's 'reflect', modules/hifigan/mel_utils.py:66-71, pads < L);
+ * "center" is pad_l = pad_r = n_fft / 2.  n_frames = dsv_stft_frames(L, ...) = 1 + (L + pad_l + pad_r - n_fft) / hop (-1: not one frame).
+ * `lengths` (device int32 [B], or NULL): valid samples per row; a row then has 1 + (len + pad_l + pad_r - n_fft) / hop valid frames (0 when
+ * that is not one frame; padding reflects about the row's own end), written to frames_out [B] (device, or NULL).  FRAMES AT OR BEYOND A ROW'S
+ * VALID COUNT ARE WRITTEN AS EXACTLY 0 by dsv_stft and dsv_logmel - the library's padding value for mels. */
+#define DSV_STFT_BASIS_FWD 0
+#define DSV_STFT_BASIS_INV 1
+#define DSV_STFT_PAD_CONSTANT 0
+#define DSV_STFT_PAD_REFLECT 1
+int64_t dsv_stft_basis_floats(int32_t n_fft, int32_t which);
+int dsv_stft_make_basis(int32_t n_fft, int32_t win_length, float* fwd, float* inv, void* stream);
+int64_t dsv_stft_frames(int64_t L, int32_t n_fft, int32_t hop, int32_t pad_l, int32_t pad_r);
+
+/* librosa.stft / torch.stft (vocoders/vocoder_utils.py:10; modules/hifigan/mel_utils.py:70-71 with complex=True): wav [B][L] ->
+ * spec [B][n_fft / 2 + 1][n_frames][2], (re, im) interleaved - the memory of a complex64 tensor [B][n_bins][n_frames], torch.stft's layout.
+ * subtract != 0 fuses the spectral subtraction of vocoders/vocoder_utils.py:11-13, np.clip(|S| - v, 0) * exp(i angle(S)) up to rounding:
+ * S' = S * max(|S| - v, 0) / |S| (0 where |S| = 0); the unfiltered spectrum is never written. */
+int dsv_stft(const float* wav, const int32_t* lengths, const float* fwd_basis, float* spec, int32_t* frames_out, int32_t B, int32_t L,
+             int32_t n_fft, int32_t hop, int32_t pad_l, int32_t pad_r, int32_t pad_mode, int32_t subtract, float v, void* stream);
+
+/* librosa.istft (vocoders/vocoder_utils.py:14) as diffsinger_amd.vocoder.denoise restates it: inverse real DFT of every frame (the imaginary
+ * parts of bin 0 and bin n_fft / 2 are ignored, as irfft does) times the synthesis window, overlap-added, divided by the window
+ * sum-of-squares where that exceeds FLT_MIN, trimmed by n_fft / 2 per side when center != 0.  Two launches: the windowed frames
+ * [B][n_frames][n_fft] go through `workspace` (dsv_istft_workspace_floats floats), then every output sample GATHERS its contributing frames
+ * in ascending frame order (the order of the host loop) - a fused form would need 64 + 2 (n_fft / hop - 1) frames of n_fft floats in LDS,
+ * 280 KiB at 1024 / 256.  wav [B][L_out]: L_out is the caller's row length, dsv_istft_samples(n_frames, ...) = n_fft + hop (n_frames - 1)
+ * [- 2 (n_fft / 2)] samples of it are signal (per row: by frame_counts [B], device int32 or NULL), the rest is written 0. */
+int64_t dsv_istft_samples(int64_t n_frames, int32_t n_fft, int32_t hop, int32_t center);
+int64_t dsv_istft_workspace_floats(int32_t B, int64_t n_frames, int32_t n_fft);
+int dsv_istft(const float* spec, const int32_t* frame_counts, const float* inv_basis, float* workspace, float* wav, int32_t B,
+              int32_t n_frames, int32_t L_out, int32_t n_fft, int32_t hop, int32_t center, void* stream);
+
+/* Log-mel analysis in one launch - process_utterance (data_gen/tts/data_gen_utils.py:122-134, behind vocoders/pwg.py:105-122 wav2spec) and
+ * mel_spectrogram (modules/hifigan/mel_utils.py:59-76):
+ *     x = clamp ? clip(wav, -1, 1) : wav;  S = stft(x);  mag = sqrt(re^2 + im^2 + mag_eps);  mel = mel_basis [M][n_bins] . mag
+ *     out[b][frame][m] = log(max(mel, floor))       natural (log10 = 0) or base 10 (log10 != 0), evaluated in float64 and rounded once
+ * mel_basis is DATA of the caller (M <= 128, row-major; librosa.filters.mel(...) or diffsinger_amd.stft.mel_filterbank); out
+ * [B][n_frames][M], the [T, 80] layout of the library's mels; linear (or NULL) [B][n_frames][n_bins] receives mag.
+ *   pwg:     pad_l = pad_r = n_fft / 2 constant, clamp 0, mag_eps 0, floor eps (wav2spec_eps), log10 1
+ *   hifigan: pad_l = pad_r = (n_fft - hop) / 2 reflect, clamp 1, mag_eps 1e-9, floor 1e-5, log10 0 */
+int dsv_logmel(const float* wav, const int32_t* lengths, const float* fwd_basis, const float* mel_basis, float* out, float* linear,
+               int32_t* frames_out, int32_t B, int32_t L, int32_t n_fft, int32_t hop, int32_t pad_l, int32_t pad_r, int32_t pad_mode,
+               int32_t clamp, int32_t M, float mag_eps, float floor, int32_t log10, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
