@@ -6,6 +6,7 @@
 #include "dsd_split.hpp"
 #include "dsd_loop_split.hpp"
 #include "dsd_loop_wino.hpp"
+#include "dsd_loop_wino_sa.hpp"
 #include "dsd_lat_wino.hpp"
 
 #include <cmath>
@@ -280,8 +281,11 @@ extern "C" int dsd_create(const dsd_config* cfg, int device, dsd_handle** out) {
         (void)hipFuncSetAttribute((const void*)k_lat_conv_w<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLatConvWLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_lat_conv_w<4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLatConvWLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_lat_conv_w<8>, hipFuncAttributeMaxDynamicSharedMemorySize, kLatConvWLdsBytes);
+        // (k_loop_wino, the form k_loop_wino_sa replaced on this path, stays instantiated: tests/golden/kernel_isa_hashes.json lists its device code)
         (void)hipFuncSetAttribute((const void*)k_loop_wino<HEAD_DDPM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopWinoLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_loop_wino<HEAD_PLMS, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopWinoLdsBytes);
+        (void)hipFuncSetAttribute((const void*)k_loop_wino_sa<HEAD_DDPM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopWinoLdsBytes);
+        (void)hipFuncSetAttribute((const void*)k_loop_wino_sa<HEAD_PLMS, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopWinoLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_head<HEAD_EPS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kHeadLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_head<HEAD_DDPM, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kHeadLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_head<HEAD_DDPM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kHeadLdsBytes);
@@ -1074,11 +1078,11 @@ static int run_persistent(dsd_handle* h, int kind, int k_step, int interval, hip
             else DSD_LAUNCH_SPLIT(0);
 #undef DSD_LAUNCH_SPLIT
         } else if (wino) {
-            // Winograd F(2,3) form of the dilated convolution (dsd_loop_wino.hpp): the default of this path
+            // Winograd F(2,3) form of the dilated convolution (dsd_loop_wino.hpp; k_loop_wino_sa, dsd_loop_wino_sa.hpp): the default of this path
             const LoopWinoParams q{p, h->w1w, (unsigned)((size_t)h->L * kWnSteps * kWnStepBytes), h->wino_touch};
             const dim3 grid((unsigned)p.n_tiles), block(kThreads);
-            if (kind == 0) hipLaunchKernelGGL((k_loop_wino<HEAD_DDPM, 4>), grid, block, kLoopWinoLdsBytes, s, q);
-            else hipLaunchKernelGGL((k_loop_wino<HEAD_PLMS, 4>), grid, block, kLoopWinoLdsBytes, s, q);
+            if (kind == 0) hipLaunchKernelGGL((k_loop_wino_sa<HEAD_DDPM, 4>), grid, block, kLoopWinoLdsBytes, s, q);
+            else hipLaunchKernelGGL((k_loop_wino_sa<HEAD_PLMS, 4>), grid, block, kLoopWinoLdsBytes, s, q);
         } else if (kind == 0) hipLaunchKernelGGL((k_loop<HEAD_DDPM>), dim3((unsigned)p.n_tiles), dim3(kThreads), kLoopLdsBytes, s, p);
         else hipLaunchKernelGGL((k_loop<HEAD_PLMS>), dim3((unsigned)p.n_tiles), dim3(kThreads), kLoopLdsBytes, s, p);
         HIP_TRY(hipGetLastError());

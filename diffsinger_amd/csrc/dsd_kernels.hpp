@@ -204,6 +204,54 @@ struct GemmPipe {
             step<5>(acc, it);
         }
     }
+    // The same walk for chunk bounds known at COMPILE time, fully unrolled: chunks [BEGIN, END), BEGIN a multiple of 6 as in run().  The same
+    // loads, stage rotation and fences as step<I>, chunk by chunk - but no back edge.  At the back edge of run() hipcc copies the whole
+    // accumulator set every iteration: in the VGPR form (-amdgpu-mfma-vgpr-form=1) an MFMA's destination is not tied to its C operand, the
+    // allocator lets the chain of a group of six end in other registers than it began in, and the loop-carried value goes back with one
+    // v_mov_b64 per register pair behind the s_nop that waits for the last MFMA - each a vector-ALU instruction paid in matrix time beside
+    // fp32 MFMAs.  Straight-line code has nothing to carry.
+    // The accumulators are rows [MB0, MB0 + NMB) of a set of NACC row blocks, so that a pipe over some rows of a set (the skip rows of the
+    // persistent Winograd loop's out-projection, which live across the layers) multiplies them where they are.
+    template <int I, int MB0, int NACC>
+    __device__ __forceinline__ void step_at(f32x16 (&acc)[NACC][NB], int it) {
+        static_assert(MB0 >= 0 && MB0 + NMB <= NACC, "row blocks of the accumulator set");
+        lda(a[(I + STAGES - 1) % STAGES], 6 * it + I + STAGES - 1);
+        ldb(b[(I + 1) & 1], it, I + 1);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+#pragma unroll
+            for (int mb = 0; mb < NMB; ++mb) {
+                const float4& am = a[I % STAGES][mb];
+                const float av = (s == 0) ? am.x : (s == 1) ? am.y : (s == 2) ? am.z : am.w;
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) acc[MB0 + mb][nb] = mfma32(av, b[I & 1][s][nb], acc[MB0 + mb][nb]);
+            }
+        }
+        pattern();
+        DSD_SB();
+    }
+    template <int BEGIN, int END, int MB0 = 0, int NACC>
+    __device__ __forceinline__ void run_static(f32x16 (&acc)[NACC][NB]) {
+        static_assert(BEGIN % 6 == 0, "begin at a multiple of the register rotation period");
+        run_static_<BEGIN, END, MB0, NACC>(acc);
+    }
+    template <int KC, int END, int MB0, int NACC>
+    __device__ __forceinline__ void run_static_(f32x16 (&acc)[NACC][NB]) {
+        if constexpr (KC < END) {
+            step_at<KC % 6, MB0, NACC>(acc, KC / 6);
+            run_static_<KC + 1, END, MB0, NACC>(acc);
+        }
+    }
+    // chunks [0, end) for a RUN-TIME end in [1, NMAX] (wave-uniform) without a back edge: one fully unrolled walk per chunk count behind a
+    // chain of scalar tests.  (Whole groups of six behind one test each and a tail per length is less code, but the accumulators then meet
+    // in a phi between two MFMAs of the contraction and the copies are back: seen in the disassembly.)  For the input projection of the
+    // persistent Winograd loop: end = mel bins / 8 <= 12, once per evaluation.  An end outside [1, NMAX] multiplies NOTHING: the caller
+    // guarantees the range (dsd_create refuses mel_bins outside 1..kMPad).
+    template <int NMAX>
+    __device__ __forceinline__ void run_bounded(f32x16 (&acc)[NMB][NB], int end) {
+        if (end == NMAX) run_static<0, NMAX>(acc);
+        else if constexpr (NMAX > 1) run_bounded<NMAX - 1>(acc, end);
+    }
     // The same walk for a RUN-TIME chunk count with the whole groups of six as ONE basic block (one branch per six chunks) and the tail
     // behind it.  With `end` unknown at compile time every `break` above ends a block; hipcc then sinks the prefetch loads of the steps
     // across the blocks (seen in the disassembly: the six A loads of an iteration issued together behind its fifth chunk, s_waitcnt

@@ -75,7 +75,7 @@ train)
 looppmc)
     timeout 200 python tools/loop_timeline.py $O/loop_timeline.json round=$TAG > $O/loop_timeline.txt 2>&1
     pmc3 pmc python $R/tools/profile_loop.py 3
-    python tools/pmc_summary.py $O/pmc 'k_loop_wino' $O/loop_pmc.txt $O/loop_pmc.json frames=8192 'kernel_tag=k_loop_wino<1, 4>' round=$TAG > $O/pmc_summary.log 2>&1
+    python tools/pmc_summary.py $O/pmc 'k_loop_wino_sa<1' $O/loop_pmc.txt $O/loop_pmc.json frames=8192 'kernel_tag=k_loop_wino<1, 4>' round=$TAG > $O/pmc_summary.log 2>&1
     tail -12 $O/loop_pmc.txt; tail -5 $O/loop_timeline.txt ;;
 fs2pmc)
     pmc3 pmc_fs2 python $R/bench.py --row fs2 --steps 3 --warmup 1 --no-cpu-baseline

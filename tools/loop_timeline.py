@@ -82,7 +82,8 @@ if len(sys.argv) > 1:
         summary[k_] = v_
     kname = ('k_loop_wino<1, 4>' if WINO else 'k_loop<1>') if not SPLIT else None
     summary['kernel_tag'], summary['build_id'] = kname, binary_id()
-    hits = {n: h for n, h in kernel_isa().items() if kname and n.startswith(kname)}
+    iname = 'k_loop_wino_sa<1, 4>' if WINO and not SPLIT else kname       # kernel_tag is bench.py's name of the Winograd loop; this is the kernel it launches
+    hits = {n: h for n, h in kernel_isa().items() if iname and n.startswith(iname)}
     if len(hits) == 1:
         (summary['kernel_isa_name'], summary['kernel_isa']), = hits.items()
     summary['phase_cycles_mean'] = sum(summary['phase_cycles']) / len(summary['phase_cycles'])
