@@ -8,12 +8,15 @@ Public surface mirrors the reference's own plugin API for this path:
     GaussianDiffusion(phone_encoder, out_dims, denoise_fn, timesteps, K_step, loss_type, betas, spec_min, spec_max)
                                         usr/diff/shallow_diffusion_tts.py:71  (+ .inference(cond, ...))
     register(*registries)               rebinds 'wavenet' (and adds 'wavenet_hip') in the reference's registries
+    STFTLoss, MultiResolutionSTFTLoss   modules/parallel_wavegan/losses/stft_loss.py:76, :109 (+ the operators under them: stft_adjoint_op,
+                                        spectral_loss_op; diffsinger_amd/stft_loss.py)
 
 Importing the package does not load the HIP library; constructing an engine does, and fails loudly if
 libdsdenoise.so is missing (no CPU fallback)."""
 from .hparams import hparams, use_preset  # noqa: F401
 
-__all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiffusion', 'register', 'hparams', 'use_preset']
+__all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiffusion', 'register', 'hparams', 'use_preset',
+           'STFTLoss', 'MultiResolutionSTFTLoss', 'stft_adjoint_op', 'spectral_loss_op']
 
 
 def __getattr__(name):      # lazy: torch-heavy modules load on first use
@@ -26,4 +29,7 @@ def __getattr__(name):      # lazy: torch-heavy modules load on first use
     if name in ('DIFF_DECODERS', 'register'):
         from . import registry
         return getattr(registry, name)
+    if name in ('STFTLoss', 'MultiResolutionSTFTLoss', 'stft_adjoint_op', 'spectral_loss_op'):
+        from . import stft_loss
+        return getattr(stft_loss, name)
     raise AttributeError(name)

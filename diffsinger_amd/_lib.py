@@ -36,7 +36,9 @@ SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'ds
                'dsv_fold_factor', 'dsv_set_fold', 'dsv_conv1d_folded', 'dsv_chain_fold', 'dsv_chain_supported', 'dsv_resblock_chain', 'dsv_resblock_chain_multi', 'dsv_resblock_chain_sum', 'dsv_set_chain_variant', 'dsv_debug_chain_timeline',
                'dsv_pwg_first', 'dsv_pwg_upsample', 'dsv_pwg_layer',
                'dsv_stft_basis_floats', 'dsv_stft_make_basis', 'dsv_stft_frames', 'dsv_stft', 'dsv_istft_samples', 'dsv_istft_workspace_floats', 'dsv_istft',
-               'dsv_logmel']
+               'dsv_logmel',
+               'dsv_stft_make_adjoint_basis', 'dsv_stft_adjoint_workspace_floats', 'dsv_stft_adjoint', 'dsv_spectral_loss_workspace_floats', 'dsv_spectral_loss',
+               'dsv_spectral_loss_backward']
 
 _fp = C.POINTER(C.c_float)
 _fpp = C.POINTER(C.c_void_p)
@@ -220,6 +222,14 @@ def load():
     lib.dsv_istft_workspace_floats.restype = i64
     lib.dsv_istft.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.dsv_logmel.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp]
+    lib.dsv_stft_make_adjoint_basis.argtypes = [i32, i32, vp, vp]
+    lib.dsv_stft_adjoint_workspace_floats.argtypes = [i32, i64, i32]
+    lib.dsv_stft_adjoint_workspace_floats.restype = i64
+    lib.dsv_stft_adjoint.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.dsv_spectral_loss_workspace_floats.argtypes = [i64]
+    lib.dsv_spectral_loss_workspace_floats.restype = i64
+    lib.dsv_spectral_loss.argtypes = [vp, vp, vp, vp, i64, vp]
+    lib.dsv_spectral_loss_backward.argtypes = [vp, vp, vp, vp, vp, i64, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('dsd_abi_version',):

@@ -22,7 +22,8 @@ static void stft_plan(int n_fft, int hop, int& KC, int& RL, size_t& lds_bytes) {
 }
 
 extern "C" int64_t dsv_stft_basis_floats(int32_t n_fft, int32_t which) {
-    if (!stft_nfft_ok(n_fft) || which < 0 || which > 1) return -1;
+    if (!stft_nfft_ok(n_fft) || which < 0 || which > DSV_STFT_BASIS_ADJ)
+        return fail(DSD_ERR_INVALID, "dsv_stft_basis_floats: n_fft=%d is not one of 256, 512, 1024, 2048, or which=%d is not a basis (0 forward, 1 inverse, 2 adjoint)", n_fft, which);
     return (int64_t)n_fft * n_fft + (which == DSV_STFT_BASIS_INV ? n_fft : 0);
 }
 

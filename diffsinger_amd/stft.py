@@ -21,6 +21,7 @@ SUPPORTED_N_FFT = (256, 512, 1024, 2048)
 MAX_MEL_BINS = 128
 _PAD_MODES = {'constant': 0, 'reflect': 1}
 _BASES: dict = {}
+_ADJ_BASES: dict = {}
 _MEL_BASES: dict = {}
 
 
@@ -96,11 +97,49 @@ def bases(device, n_fft: int, win_length: int):
     return fwd, inv
 
 
+def adjoint_basis(device, n_fft: int, win_length: int):
+    """The transposed forward basis of (n_fft, win_length) on `device` (dsv_stft_make_adjoint_basis), built once and cached like `bases`: the
+    build is refused inside a graph capture - a differentiable stft_op call builds it in its FORWARD, so one warm-up call is enough."""
+    device = torch.device(device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), n_fft, win_length)
+    hit = _ADJ_BASES.get(key)
+    if hit is not None:
+        return hit
+    _check_geometry(n_fft, 1, win_length)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f'the adjoint STFT basis of (n_fft={n_fft}, win_length={win_length}) is not built yet and cannot be built inside a graph '
+                           f'capture: call diffsinger_amd.stft.adjoint_basis(device, {n_fft}, {win_length}) first')
+    lib = _lib.load()
+    dev = torch.device('cuda', key[0])
+    adj = torch.empty(lib.dsv_stft_basis_floats(n_fft, 2), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(lib.dsv_stft_make_adjoint_basis(n_fft, win_length, adj.data_ptr(), _stream(dev)), 'dsv_stft_make_adjoint_basis')
+    torch.cuda.current_stream(dev).synchronize()          # one-time: the buffer is used from any stream afterwards
+    _ADJ_BASES[key] = adj
+    return adj
+
+
+def _stft_launch(x, lens, n_fft, hop, win_length, pl, pr, pad_mode, subtract, fc):
+    """dsv_stft on validated arguments: x [B][L] float32 contiguous -> float32 [B][n_bins][n_frames][2]"""
+    B, L = x.shape
+    T = n_frames(L, n_fft, hop, pl, pr)
+    fwd, _ = bases(x.device, n_fft, win_length)
+    spec = torch.empty(B, n_fft // 2 + 1, T, 2, device=x.device, dtype=torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dsv_stft(x.data_ptr(), lens.data_ptr() if lens is not None else None, fwd.data_ptr(), spec.data_ptr(),
+                                fc.data_ptr() if fc is not None else None, B, L, n_fft, hop, pl, pr, _PAD_MODES[pad_mode],
+                                0 if subtract is None else 1, 0.0 if subtract is None else float(subtract), _stream(x.device)), 'dsv_stft')
+    return spec
+
+
 def stft_op(wav, *, n_fft, hop, win_length=None, center=True, pad_mode='constant', pad=None, lengths=None, subtract=None, return_frames=False):
     """wav [B][L] (or [L]) -> complex64 [B][n_fft / 2 + 1][n_frames], torch.stft's layout.  center: n_fft / 2 of padding per side (`pad`, an int
     or (left, right), overrides the amount); pad_mode 'constant' (zeros) or 'reflect'.  lengths [B]: valid samples per row - frames beyond a
     row's count are exactly 0.  subtract=v fuses S * max(|S| - v, 0) / |S| (the unfiltered spectrum is never written).  return_frames: also
-    the rows' valid frame counts (int32 [B], device)."""
+    the rows' valid frame counts (int32 [B], device).
+    A waveform that requires grad makes the call differentiable: its backward is the adjoint STFT (diffsinger_amd.stft_loss.stft_adjoint_op);
+    subtract= and lengths= have no gradient (NotImplementedError)."""
     win_length = n_fft if win_length is None else win_length
     _check_geometry(n_fft, hop, win_length)
     if pad_mode not in _PAD_MODES:
@@ -110,18 +149,18 @@ def stft_op(wav, *, n_fft, hop, win_length=None, center=True, pad_mode='constant
     pl, pr = _pads(n_fft, center, pad)
     if pad_mode == 'reflect' and max(pl, pr) >= L:
         raise ValueError(f'reflect padding ({pl}, {pr}) must be smaller than the signal (L={L})')
-    T = n_frames(L, n_fft, hop, pl, pr)
+    n_frames(L, n_fft, hop, pl, pr)
     if subtract is not None and not (subtract >= 0 and np.isfinite(subtract)):
         raise ValueError(f'subtract={subtract} must be finite and >= 0')
     lens = _lengths(lengths, B, x.device)
-    fwd, _ = bases(x.device, n_fft, win_length)
-    spec = torch.empty(B, n_fft // 2 + 1, T, 2, device=x.device, dtype=torch.float32)
     fc = torch.empty(B, device=x.device, dtype=torch.int32) if return_frames else None
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dsv_stft(x.data_ptr(), lens.data_ptr() if lens is not None else None, fwd.data_ptr(), spec.data_ptr(),
-                                fc.data_ptr() if fc is not None else None, B, L, n_fft, hop, pl, pr, _PAD_MODES[pad_mode],
-                                0 if subtract is None else 1, 0.0 if subtract is None else float(subtract), _stream(x.device)), 'dsv_stft')
+    if x.requires_grad and torch.is_grad_enabled():
+        if subtract is not None or lengths is not None:
+            raise NotImplementedError('stft_op: subtract= and lengths= have no gradient (detach the waveform, or call it without them)')
+        from .stft_loss import StftFunction
+        spec = StftFunction.apply(x, n_fft, hop, win_length, pl, pr, pad_mode, fc)
+    else:
+        spec = _stft_launch(x, lens, n_fft, hop, win_length, pl, pr, pad_mode, subtract, fc)
     out = torch.view_as_complex(spec)
     return (out, fc) if return_frames else out
 

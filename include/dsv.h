@@ -232,6 +232,40 @@ int dsv_logmel(const float* wav, const int32_t* lengths, const float* fwd_basis,
                int32_t* frames_out, int32_t B, int32_t L, int32_t n_fft, int32_t hop, int32_t pad_l, int32_t pad_r, int32_t pad_mode,
                int32_t clamp, int32_t M, float mag_eps, float floor, int32_t log10, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * STFT loss: the multi-resolution STFT criterion of the vocoder trainers (modules/parallel_wavegan/losses/stft_loss.py, configured by
+ * configs/tts/pwg.yaml:77-82) - the transpose of dsv_stft and the spectral loss over two spectra, forward and backward
+ * (csrc/voc_stft_loss.hpp).  Fixed summation order, no atomics (two calls are bitwise equal), nothing allocates or synchronises, every
+ * scalar the backward needs is read from device memory: the whole forward and backward records into one graph.
+ *
+ * Adjoint STFT - the vector-Jacobian product of dsv_stft (no lengths, no subtraction): grad_spec [B][n_fft / 2 + 1][n_frames][2], the
+ * cotangent in the spectrum's own layout, -> grad_wav [B][L].  frame_grad[f][n] = sum_rows A[row][n] G[row][f] is the product dsv_istft
+ * runs (the same kernel) against a third basis, DSV_STFT_BASIS_ADJ: the forward basis transposed - the ANALYSIS window, no 1 / n_fft, no
+ * factor 2 on the interior bins; the imaginary cotangents of bin 0 and bin n_fft / 2 are ignored (the forward writes 0 there whatever the
+ * signal).  dsv_stft_basis_floats(n_fft, DSV_STFT_BASIS_ADJ) floats, filled by dsv_stft_make_adjoint_basis (on the device in float64,
+ * once per (n_fft, win_length), outside a capture).  The frame gradients go through `workspace` (dsv_stft_adjoint_workspace_floats
+ * floats); then every sample of grad_wav GATHERS the values of its position of the padded signal in ascending frame order - no division
+ * by a window sum.  Padding folds back by index arithmetic: DSV_STFT_PAD_CONSTANT drops what fell on the padding, DSV_STFT_PAD_REFLECT
+ * adds to a sample the sums of the positions that mirrored it (left mirror, then right; a short row can have both).  L, n_fft, hop, pad_l,
+ * pad_r, pad_mode are the forward call's and are refused as there. */
+#define DSV_STFT_BASIS_ADJ 2
+int dsv_stft_make_adjoint_basis(int32_t n_fft, int32_t win_length, float* adj, void* stream);
+int64_t dsv_stft_adjoint_workspace_floats(int32_t B, int64_t n_frames, int32_t n_fft);
+int dsv_stft_adjoint(const float* grad_spec, const float* adj_basis, float* workspace, float* grad_wav, int32_t B, int32_t L, int32_t n_fft,
+                     int32_t hop, int32_t pad_l, int32_t pad_r, int32_t pad_mode, void* stream);
+
+/* Spectral loss over two spectra X (the prediction) and Y (the recording), n complex elements each ((re, im) interleaved, any layout as
+ * long as both share it):  P = re^2 + im^2,  m = sqrt(max(P, 1e-7))  (stft_loss.py:26-31),
+ *     out[0] = sc  = ||ym - xm||_F / ||ym||_F  (:52)          out[1] = mag = mean |ln ym - ln xm|  (:73)
+ * One pass over X and Y with float64 sums per thread and a fixed-order tree per workgroup, partials to `workspace`
+ * (dsv_spectral_loss_workspace_floats(n) floats, 8-byte aligned; -1: n outside [1, 2^40]), one more launch adds them in index order and leaves
+ * S1 = ||ym - xm||_F and S2 = ||ym||_F there for the backward.  Backward (same X, Y, workspace; grad_out [2] = (g_sc, g_mag) ON THE DEVICE):
+ *     G = (re, im) * [ -g_sc (ym - xm) / (xm S1 S2) - g_mag sign(ln ym - ln xm) / (n P) ]     where P > 1e-7;  exactly 0 where the clamp is
+ * active.  sign(0) = 0 and a zero difference contributes 0 (X = Y gives G = 0).  The gradient is with respect to X only. */
+int64_t dsv_spectral_loss_workspace_floats(int64_t n);
+int dsv_spectral_loss(const float* X, const float* Y, float* workspace, float* out, int64_t n, void* stream);
+int dsv_spectral_loss_backward(const float* X, const float* Y, const float* workspace, const float* grad_out, float* G, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
