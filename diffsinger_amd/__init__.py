@@ -10,13 +10,17 @@ Public surface mirrors the reference's own plugin API for this path:
     register(*registries)               rebinds 'wavenet' (and adds 'wavenet_hip') in the reference's registries
     STFTLoss, MultiResolutionSTFTLoss   modules/parallel_wavegan/losses/stft_loss.py:76, :109 (+ the operators under them: stft_adjoint_op,
                                         spectral_loss_op; diffsinger_amd/stft_loss.py)
+    ParallelWaveGANDiscriminator        modules/parallel_wavegan/models/parallel_wavegan.py:207, forward and backward on HIP (+ pwg_disc_op,
+                                        lsgan_loss_op, generator_loss, discriminator_loss: modules/hifigan/hifigan.py:337-365;
+                                        diffsinger_amd/pwg_disc.py)
 
 Importing the package does not load the HIP library; constructing an engine does, and fails loudly if
 libdsdenoise.so is missing (no CPU fallback)."""
 from .hparams import hparams, use_preset  # noqa: F401
 
 __all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiffusion', 'register', 'hparams', 'use_preset',
-           'STFTLoss', 'MultiResolutionSTFTLoss', 'stft_adjoint_op', 'spectral_loss_op']
+           'STFTLoss', 'MultiResolutionSTFTLoss', 'stft_adjoint_op', 'spectral_loss_op',
+           'ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss']
 
 
 def __getattr__(name):      # lazy: torch-heavy modules load on first use
@@ -32,4 +36,7 @@ def __getattr__(name):      # lazy: torch-heavy modules load on first use
     if name in ('STFTLoss', 'MultiResolutionSTFTLoss', 'stft_adjoint_op', 'spectral_loss_op'):
         from . import stft_loss
         return getattr(stft_loss, name)
+    if name in ('ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss'):
+        from . import pwg_disc
+        return getattr(pwg_disc, name)
     raise AttributeError(name)

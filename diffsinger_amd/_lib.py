@@ -38,7 +38,10 @@ SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'ds
                'dsv_stft_basis_floats', 'dsv_stft_make_basis', 'dsv_stft_frames', 'dsv_stft', 'dsv_istft_samples', 'dsv_istft_workspace_floats', 'dsv_istft',
                'dsv_logmel',
                'dsv_stft_make_adjoint_basis', 'dsv_stft_adjoint_workspace_floats', 'dsv_stft_adjoint', 'dsv_spectral_loss_workspace_floats', 'dsv_spectral_loss',
-               'dsv_spectral_loss_backward']
+               'dsv_spectral_loss_backward',
+               'dsv_pwgd_tile', 'dsv_pwgd_wgrad_split', 'dsv_pwgd_wgrad_workspace_floats', 'dsv_pwgd_edge_workspace_floats', 'dsv_pwgd_layer', 'dsv_pwgd_wgrad',
+               'dsv_pwgd_first', 'dsv_pwgd_first_backward', 'dsv_pwgd_last', 'dsv_pwgd_last_backward', 'dsv_pwgd_lsgan_workspace_floats', 'dsv_pwgd_lsgan',
+               'dsv_pwgd_lsgan_backward']
 
 _fp = C.POINTER(C.c_float)
 _fpp = C.POINTER(C.c_void_p)
@@ -230,6 +233,24 @@ def load():
     lib.dsv_spectral_loss_workspace_floats.restype = i64
     lib.dsv_spectral_loss.argtypes = [vp, vp, vp, vp, i64, vp]
     lib.dsv_spectral_loss_backward.argtypes = [vp, vp, vp, vp, vp, i64, vp]
+    lib.dsv_pwgd_tile.argtypes = []
+    lib.dsv_pwgd_tile.restype = i32
+    lib.dsv_pwgd_wgrad_split.argtypes = []
+    lib.dsv_pwgd_wgrad_split.restype = i32
+    lib.dsv_pwgd_wgrad_workspace_floats.argtypes = [i32, i32]
+    lib.dsv_pwgd_wgrad_workspace_floats.restype = i64
+    lib.dsv_pwgd_edge_workspace_floats.argtypes = [i32, i32]
+    lib.dsv_pwgd_edge_workspace_floats.restype = i64
+    lib.dsv_pwgd_layer.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]
+    lib.dsv_pwgd_wgrad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.dsv_pwgd_first.argtypes = [vp, vp, vp, vp, i32, i32, f32, vp]
+    lib.dsv_pwgd_first_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    lib.dsv_pwgd_last.argtypes = [vp, vp, vp, vp, i32, i32, vp]
+    lib.dsv_pwgd_last_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]
+    lib.dsv_pwgd_lsgan_workspace_floats.argtypes = [i64]
+    lib.dsv_pwgd_lsgan_workspace_floats.restype = i64
+    lib.dsv_pwgd_lsgan.argtypes = [vp, f32, vp, vp, i64, vp]
+    lib.dsv_pwgd_lsgan_backward.argtypes = [vp, f32, vp, vp, i64, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('dsd_abi_version',):

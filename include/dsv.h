@@ -266,6 +266,52 @@ int64_t dsv_spectral_loss_workspace_floats(int64_t n);
 int dsv_spectral_loss(const float* X, const float* Y, float* workspace, float* out, int64_t n, void* stream);
 int dsv_spectral_loss_backward(const float* X, const float* Y, const float* workspace, const float* grad_out, float* G, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * PWG discriminator: ParallelWaveGANDiscriminator (modules/parallel_wavegan/models/parallel_wavegan.py:207-300; configs/tts/pwg.yaml
+ * discriminator_params: 10 layers, 64 channels, kernel 3, LeakyReLU(0.2)) forward AND backward, and the LSGAN criterion
+ * (modules/hifigan/hifigan.py:337-365) - csrc/pwg_disc.hpp.  Activations [B][64][LS(T)] channel-major, waveform-like rows [B][LS(T)]; every call
+ * leaves [T, LS) of its outputs at zero.  Exact fp32 (MFMA with fp32 accumulation), no atomics, fixed summation order (two calls are bitwise
+ * equal); nothing allocates or synchronises, every scalar is read from device memory: forward, loss and backward record into one graph.
+ * B in [1, 65535], T in [1, 2^30], 0 < slope < 1, 1 <= dil <= 8; anything else is refused with DSD_ERR_INVALID before any launch.
+ *
+ * dsv_pwgd_tile(): samples per workgroup of dsv_pwgd_layer.  dsv_pwgd_wgrad_split(): samples per workgroup of dsv_pwgd_wgrad; its workspace is
+ * dsv_pwgd_wgrad_workspace_floats(B, T) = B * ceil(T / split) * (64 * 64 * 3 + 64) floats (-1: bad shape).
+ *
+ * dsv_pwgd_layer: one 64 -> 64 layer (kernel 3, dilation dil, 'same' zero padding), one launch.
+ *   backward == 0:  out = leaky_relu(W in + bias, slope);  w_packed = dsv_pack_weight of the [64][192][1] matrix with columns tap * 64 + ci
+ *                   (tap 0 reads t - dil); bias [64] or NULL; saved must be NULL.
+ *   backward != 0:  out = (W^T * in) m - `in` the gradient with respect to this layer's pre-activation, out the gradient with respect to the
+ *                   pre-activation of the layer below; m = 1 where saved (that layer's POST-activation, [B][64][LS]) > 0, else slope (a saved
+ *                   value of exactly 0 takes the slope, as autograd does for an in-place LeakyReLU); saved NULL: no mask.  w_packed =
+ *                   dsv_pack_weight of [64][192][1] with row ci, column tap * 64 + co = W[co][ci][2 - tap]; bias must be NULL.
+ *   out must not alias in.  Several layers' matrices may be packed by ONE dsv_pack_weight call of [n * 64][192][1]: layer i's stream starts
+ *   2 * i * 24 * 256 floats into the buffer.
+ * dsv_pwgd_wgrad: dw[co][ci][k] = sum_b sum_t g[b][co][t] a_prev[b][ci][t + (k - 1) dil] (torch layout [64][64][3]), db[co] = sum_b sum_t
+ *   g[b][co][t] (db NULL: not written).  Two launches: split partials on the MFMA, then the splits added in index order in float64.
+ * dsv_pwgd_first: x [B][LS] -> out [B][64][LS] = leaky_relu(conv(x; w [64][1][3], dilation 1) + bias).  dsv_pwgd_first_backward: from g0 (the
+ *   gradient with respect to the first layer's pre-activation) dw [64][3], db [64] (or NULL), and dx [B][LS] - only when dx is not NULL (one
+ *   launch less).  dsv_pwgd_last: a [B][64][LS] -> out [B][LS] = conv(a; w [1][64][3], dilation 1) + bias[0], no activation.
+ *   dsv_pwgd_last_backward: from gp [B][LS] (zero in [T, LS)) dw [64][3], db [1] (or NULL) and ga = (w^T * gp) m(a) [B][64][LS].  The parameter
+ *   gradients of both use a workspace of dsv_pwgd_edge_workspace_floats(B, T) floats and sum in float64 in a fixed order.
+ * LSGAN: out[0] = mean((d[i] - target)^2) over n floats (float64 partial sums in `workspace`, dsv_pwgd_lsgan_workspace_floats(n) floats, 8-byte
+ *   aligned; -1: n outside [1, 2^40]); backward G[i] = 2 (d[i] - target) / n * grad_out[0], grad_out ON THE DEVICE. */
+int32_t dsv_pwgd_tile(void);
+int32_t dsv_pwgd_wgrad_split(void);
+int64_t dsv_pwgd_wgrad_workspace_floats(int32_t B, int32_t T);
+int64_t dsv_pwgd_edge_workspace_floats(int32_t B, int32_t T);
+int dsv_pwgd_layer(const float* in, const float* w_packed, const float* bias, const float* saved, float* out, int32_t B, int32_t T, int32_t dil,
+                   float slope, int32_t backward, void* stream);
+int dsv_pwgd_wgrad(const float* g, const float* a_prev, float* workspace, float* dw, float* db, int32_t B, int32_t T, int32_t dil, void* stream);
+int dsv_pwgd_first(const float* x, const float* w, const float* bias, float* out, int32_t B, int32_t T, float slope, void* stream);
+int dsv_pwgd_first_backward(const float* g0, const float* x, const float* w, float* workspace, float* dw, float* db, float* dx, int32_t B,
+                            int32_t T, void* stream);
+int dsv_pwgd_last(const float* a, const float* w, const float* bias, float* out, int32_t B, int32_t T, void* stream);
+int dsv_pwgd_last_backward(const float* gp, const float* a, const float* w, float* workspace, float* dw, float* db, float* ga, int32_t B, int32_t T,
+                           float slope, void* stream);
+int64_t dsv_pwgd_lsgan_workspace_floats(int64_t n);
+int dsv_pwgd_lsgan(const float* d, float target, float* workspace, float* out, int64_t n, void* stream);
+int dsv_pwgd_lsgan_backward(const float* d, float target, const float* grad_out, float* G, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
