@@ -13,6 +13,9 @@ Public surface mirrors the reference's own plugin API for this path:
     ParallelWaveGANDiscriminator        modules/parallel_wavegan/models/parallel_wavegan.py:207, forward and backward on HIP (+ pwg_disc_op,
                                         lsgan_loss_op, generator_loss, discriminator_loss: modules/hifigan/hifigan.py:337-365;
                                         diffsinger_amd/pwg_disc.py)
+    pe_losses(output, sample, hp), pe_training_step(model, sample, hp)
+                                        PitchExtractionTask.run_model / ._training_step (tasks/tts/pe.py:111-155) on the HIP PitchExtractor
+                                        (diffsinger_amd/pe.py)
 
 Importing the package does not load the HIP library; constructing an engine does, and fails loudly if
 libdsdenoise.so is missing (no CPU fallback)."""
@@ -20,7 +23,8 @@ from .hparams import hparams, use_preset  # noqa: F401
 
 __all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiffusion', 'register', 'hparams', 'use_preset',
            'STFTLoss', 'MultiResolutionSTFTLoss', 'stft_adjoint_op', 'spectral_loss_op',
-           'ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss']
+           'ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss',
+           'pe_losses', 'pe_training_step']
 
 
 def __getattr__(name):      # lazy: torch-heavy modules load on first use
@@ -39,4 +43,7 @@ def __getattr__(name):      # lazy: torch-heavy modules load on first use
     if name in ('ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss'):
         from . import pwg_disc
         return getattr(pwg_disc, name)
+    if name in ('pe_losses', 'pe_training_step'):
+        from . import pe
+        return getattr(pe, name)
     raise AttributeError(name)

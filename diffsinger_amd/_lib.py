@@ -28,6 +28,8 @@ SYMBOLS_FS2 = ['dsf_padded_frames', 'dsf_packed_floats', 'dsf_pack_weight', 'dsf
                'dsf_conv1d_dilated', 'dsf_set_conv_split', 'dsf_wgrad_workspace_floats', 'dsf_conv1d_wgrad', 'dsf_bias_grad',
                'dsf_train_add_step', 'dsf_train_rowsum', 'dsf_train_gate', 'dsf_train_gate_bwd', 'dsf_train_res_skip', 'dsf_train_res_skip_bwd',
                'dsf_channel_affine', 'dsf_group_norm', 'dsf_adamw_step',
+               'dsf_batch_norm_train', 'dsf_batch_norm_train_bwd', 'dsf_group_norm_bwd_workspace_floats', 'dsf_group_norm_bwd',
+               'dsf_f0_loss_workspace_floats', 'dsf_f0_loss', 'dsf_f0_loss_bwd',
                'dsf_stack_workspace_floats', 'dsf_set_stack_mode', 'dsf_set_stack_conv', 'dsf_get_stack_conv', 'dsf_set_wgrad_dual', 'dsf_debug_trb_timeline', 'dsf_stack_offsets', 'dsf_stack_forward', 'dsf_stack_backward', 'dsf_wgrad2_workspace_floats', 'dsf_conv1d_wgrad2', 'dsf_wgrad_probe', 'dsf_wgrad_probe_read',
                'dsf_fs2_loss_workspace_floats', 'dsf_mel_loss', 'dsf_mel_loss_bwd', 'dsf_dur_loss', 'dsf_dur_loss_bwd', 'dsf_length_regulate']
 
@@ -179,6 +181,15 @@ def load():
     lib.dsf_adamw_step.argtypes = [vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, i64, vp, vp]
     lib.dsf_channel_affine.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
     lib.dsf_group_norm.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]
+    lib.dsf_batch_norm_train.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, vp]
+    lib.dsf_batch_norm_train_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.dsf_group_norm_bwd_workspace_floats.argtypes = [i32, i32]
+    lib.dsf_group_norm_bwd_workspace_floats.restype = i64
+    lib.dsf_group_norm_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]
+    lib.dsf_f0_loss_workspace_floats.argtypes = []
+    lib.dsf_f0_loss_workspace_floats.restype = i64
+    lib.dsf_f0_loss.argtypes = [vp, i64, i64, i64, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp]
+    lib.dsf_f0_loss_bwd.argtypes = [vp, i64, i64, i64, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp]
     lib.dsf_fs2_loss_workspace_floats.argtypes = [i32, i32, i32]
     lib.dsf_fs2_loss_workspace_floats.restype = i64
     lib.dsf_mel_loss.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, f32, i32, i32, f32, f32, vp, vp, vp, vp]

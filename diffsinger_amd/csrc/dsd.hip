@@ -1533,3 +1533,4 @@ extern "C" int dsd_debug_layer_timeline(dsd_handle* h, int32_t layer, int32_t t,
 #include "voc_stft_abi.hpp"
 #include "voc_stft_loss_abi.hpp"
 #include "pwg_disc_abi.hpp"
+#include "pe_train.hpp"

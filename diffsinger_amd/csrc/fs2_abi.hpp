@@ -98,11 +98,12 @@ static int fs_conv_launch(const float* in, const float* wpacked, const float* bi
 extern "C" int dsf_layer_norm(const float* in, const float* gamma, const float* beta, float* out, int32_t B, int32_t C, int32_t T,
                               float eps, int32_t relu_in, const float* keep, void* stream) {
     if (!in || !gamma || !beta || !out) return fail(DSD_ERR_INVALID, "dsf_layer_norm: null argument");
-    if (C != kC) return fail(DSD_ERR_INVALID, "dsf_layer_norm: this build normalises over %d channels (got %d)", kC, C);
+    if (C < 8 || C > kC || (C % 8)) return fail(DSD_ERR_INVALID, "dsf_layer_norm: a multiple of 8 channels up to %d is supported (got %d)", kC, C);
     if (B < 1 || T < 1) return fail(DSD_ERR_INVALID, "dsf_layer_norm: bad shape");
     FsLnParams p{};
     p.in = in; p.out = out; p.gamma = gamma; p.beta = beta; p.keep = keep; p.T = T; p.TS = fs_ts(T); p.eps = eps; p.relu_in = relu_in;
-    hipLaunchKernelGGL(k_fs_ln, dim3((unsigned)(p.TS / 32), (unsigned)B), dim3(kThreads), 0, (hipStream_t)stream, p);
+    if (C == kC) hipLaunchKernelGGL(k_fs_ln, dim3((unsigned)(p.TS / 32), (unsigned)B), dim3(kThreads), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(k_fs_ln_any, dim3((unsigned)(p.TS / 32), (unsigned)B), dim3(kThreads), 0, (hipStream_t)stream, p, (int)C);
     HIP_TRY(hipGetLastError());
     return DSD_OK;
 }
@@ -135,15 +136,16 @@ extern "C" int64_t dsf_ln_bwd_workspace_floats(int32_t B, int32_t T) {
 extern "C" int dsf_layer_norm_bwd(const float* x, const float* gamma, const float* dy, const float* keep, float* dx, float* dgamma, float* dbeta,
                                   float* ws, int32_t B, int32_t C, int32_t T, float eps, int32_t relu_in, void* stream) {
     if (!x || !gamma || !dy || !dx || !dgamma || !dbeta || !ws) return fail(DSD_ERR_INVALID, "dsf_layer_norm_bwd: null argument");
-    if (C != kC) return fail(DSD_ERR_INVALID, "dsf_layer_norm_bwd: this build normalises over %d channels (got %d)", kC, C);
+    if (C < 8 || C > kC || (C % 8)) return fail(DSD_ERR_INVALID, "dsf_layer_norm_bwd: a multiple of 8 channels up to %d is supported (got %d)", kC, C);
     if (B < 1 || T < 1) return fail(DSD_ERR_INVALID, "dsf_layer_norm_bwd: bad shape");
     FsLnBwdParams p{};
     p.x = x; p.dy = dy; p.gamma = gamma; p.keep = keep; p.dx = dx; p.part = ws; p.T = T; p.TS = fs_ts(T); p.eps = eps; p.relu_in = relu_in;
     const int ntile = p.TS / 32;
-    hipLaunchKernelGGL(k_fs_ln_bwd, dim3((unsigned)ntile, (unsigned)B), dim3(kThreads), 0, (hipStream_t)stream, p);
-    // partials are [B * ntile][dgamma 256 | dbeta 256]
-    hipLaunchKernelGGL(k_fs_colsum, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, dgamma, B * ntile, 256, 512);
-    hipLaunchKernelGGL(k_fs_colsum, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws + 256, dbeta, B * ntile, 256, 512);
+    if (C == kC) hipLaunchKernelGGL(k_fs_ln_bwd, dim3((unsigned)ntile, (unsigned)B), dim3(kThreads), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(k_fs_ln_bwd_any, dim3((unsigned)ntile, (unsigned)B), dim3(kThreads), 0, (hipStream_t)stream, p, (int)C);
+    // partials are [B * ntile][dgamma 256 | dbeta 256] (the first C of each)
+    hipLaunchKernelGGL(k_fs_colsum, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, dgamma, B * ntile, (int)C, 512);
+    hipLaunchKernelGGL(k_fs_colsum, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws + 256, dbeta, B * ntile, (int)C, 512);
     HIP_TRY(hipGetLastError());
     return DSD_OK;
 }

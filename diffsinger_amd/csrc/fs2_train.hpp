@@ -101,6 +101,121 @@ __global__ __launch_bounds__(kThreads) void k_fs_ln_bwd(const FsLnBwdParams p) {
     }
 }
 
+// LayerNorm forward / backward over C channels, C a multiple of 8 up to 256 (a PitchExtractor narrower than this build's 256: the predictor stack
+// of a small configuration): the decomposition of k_fs_ln / k_fs_ln_bwd with C / 8 channels per thread, read again from memory in every pass
+// instead of held in registers.  The partials keep k_fs_ln_bwd's layout (dgamma at [0, 256), dbeta at [256, 512) of every tile).
+__global__ __launch_bounds__(kThreads) void k_fs_ln_any(const FsLnParams p, const int C) {
+    __shared__ float red[8][32];
+    const int tid = threadIdx.x, tc = tid & 31, part = tid >> 5, cpp = C / 8;
+    const int t = blockIdx.x * 32 + tc, b = blockIdx.y;
+    const size_t base = ((size_t)b * C + part * cpp) * p.TS + t;
+    float s = 0.f;
+    for (int i = 0; i < cpp; ++i) {
+        float x = p.in[base + (size_t)i * p.TS];
+        if (p.relu_in) x = fmaxf(x, 0.f);
+        s += x;
+    }
+    red[part][tc] = s;
+    __syncthreads();
+    float mean = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) mean += red[q][tc];
+    mean /= (float)C;
+    __syncthreads();
+    float d = 0.f;
+    for (int i = 0; i < cpp; ++i) {
+        float x = p.in[base + (size_t)i * p.TS];
+        if (p.relu_in) x = fmaxf(x, 0.f);
+        const float e = x - mean;
+        d += e * e;
+    }
+    red[part][tc] = d;
+    __syncthreads();
+    float var = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) var += red[q][tc];
+    var /= (float)C;
+    const float rstd = 1.f / sqrtf(var + p.eps);
+    const bool tv = t < p.T;
+    float kp = 1.f;
+    if (p.keep && tv) kp = p.keep[(size_t)b * p.T + t];
+    for (int i = 0; i < cpp; ++i) {
+        const int c = part * cpp + i;
+        float x = p.in[base + (size_t)i * p.TS];
+        if (p.relu_in) x = fmaxf(x, 0.f);
+        const float y = ((x - mean) * rstd * p.gamma[c] + p.beta[c]) * kp;
+        p.out[base + (size_t)i * p.TS] = tv ? y : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_fs_ln_bwd_any(const FsLnBwdParams p, const int C) {
+    __shared__ float red[2][8][32];
+    const int tid = threadIdx.x, tc = tid & 31, part = tid >> 5, cpp = C / 8;
+    const int t = blockIdx.x * 32 + tc, b = blockIdx.y;
+    const size_t base = ((size_t)b * C + part * cpp) * p.TS + t;
+    const bool tv = t < p.T;
+    float kp = tv ? 1.f : 0.f;
+    if (p.keep && tv) kp = p.keep[(size_t)b * p.T + t];
+    float s = 0.f;
+    for (int i = 0; i < cpp; ++i) {
+        float x = p.x[base + (size_t)i * p.TS];
+        if (p.relu_in) x = fmaxf(x, 0.f);
+        s += x;
+    }
+    red[0][part][tc] = s;
+    __syncthreads();
+    float mean = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) mean += red[0][q][tc];
+    mean /= (float)C;
+    __syncthreads();
+    float d = 0.f;
+    for (int i = 0; i < cpp; ++i) {
+        float x = p.x[base + (size_t)i * p.TS];
+        if (p.relu_in) x = fmaxf(x, 0.f);
+        const float e = x - mean;
+        d += e * e;
+    }
+    red[0][part][tc] = d;
+    __syncthreads();
+    float var = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) var += red[0][q][tc];
+    var /= (float)C;
+    const float rstd = 1.f / sqrtf(var + p.eps);
+    __syncthreads();
+    float s1 = 0.f, s2 = 0.f;
+    for (int i = 0; i < cpp; ++i) {
+        float x = p.x[base + (size_t)i * p.TS];
+        if (p.relu_in) x = fmaxf(x, 0.f);
+        const float gg = p.dy[base + (size_t)i * p.TS] * kp * p.gamma[part * cpp + i];
+        s1 += gg;
+        s2 += gg * ((x - mean) * rstd);
+    }
+    red[0][part][tc] = s1;
+    red[1][part][tc] = s2;
+    __syncthreads();
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { m1 += red[0][q][tc]; m2 += red[1][q][tc]; }
+    m1 /= (float)C;
+    m2 /= (float)C;
+    float* pt = p.part + ((size_t)b * (p.TS / 32) + blockIdx.x) * 512;
+    for (int i = 0; i < cpp; ++i) {
+        const float pre = p.x[base + (size_t)i * p.TS];
+        const float x = p.relu_in ? fmaxf(pre, 0.f) : pre;
+        const float xh = (x - mean) * rstd;
+        const float g = p.dy[base + (size_t)i * p.TS] * kp;
+        float dx = rstd * (g * p.gamma[part * cpp + i] - m1 - xh * m2);
+        if (p.relu_in && !(pre > 0.f)) dx = 0.f;
+        p.dx[base + (size_t)i * p.TS] = tv ? dx : 0.f;
+        float a = g * xh, c = g;
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) { a += __shfl_xor(a, off, 32); c += __shfl_xor(c, off, 32); }
+        if (tc == 0) { pt[part * cpp + i] = a; pt[256 + part * cpp + i] = c; }
+    }
+}
+
 // out[c] = sum_r part[r * stride + c] in row order (fixed summation order), c < ncol
 __global__ __launch_bounds__(256) void k_fs_colsum(const float* __restrict__ part, float* __restrict__ out, int nrows, int ncol, int stride) {
     const int c = blockIdx.x * 256 + threadIdx.x;

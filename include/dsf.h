@@ -40,7 +40,7 @@ int dsf_pack_weight(const float* w, int32_t Co, int32_t Ci, int32_t K, float* pa
 int dsf_conv1d(const float* in, const float* wpacked, const float* bias, float* out, int32_t B, int32_t Ci, int32_t Co, int32_t K,
                int32_t T, float scale, int32_t act, const float* residual, const float* keep, void* stream);
 
-/* nn.LayerNorm over the channel axis (C = 256 on this build): EncSALayer.layer_norm1/2 and FFTBlocks.layer_norm (eps 1e-5,
+/* nn.LayerNorm over the channel axis (C = 256 on this build; any other multiple of 8 up to 256 runs a plainer kernel): EncSALayer.layer_norm1/2 and FFTBlocks.layer_norm (eps 1e-5,
  * common_layers.py:70-77, tts_modules.py:276-281,:306-307), the predictor LayerNorm(dim=1) (eps 1e-12, tts_modules.py:39-56)
  * with the preceding ReLU (relu_in = 1).  out = LN(in) * gamma + beta, times keep[b][t] if given. */
 int dsf_layer_norm(const float* in, const float* gamma, const float* beta, float* out, int32_t B, int32_t C, int32_t T, float eps,
@@ -271,6 +271,41 @@ int dsf_conv1d_wgrad2(const float* dy, const float* x, float* dw, float* db, flo
 int dsf_channel_affine(const float* x, const float* a, const float* b, const float* keep, float* y, int32_t B, int32_t C, int32_t T, void* stream);
 int dsf_group_norm(const float* x, const float* gamma, const float* beta, const float* residual, float* y, int32_t B, int32_t C, int32_t groups,
                    int32_t T, float eps, int32_t relu, void* stream);
+
+/* PitchExtractor training (PitchExtractionTask, tasks/tts/pe.py; csrc/pe_train.hpp): what the backward pass and the task's loss need beyond
+ * dsf_conv1d_wgrad / dsf_layer_norm_bwd.  fp32, channel-major [B][C][TS] with a zero tail, every sum in a fixed order (two runs are bitwise
+ * equal), no atomics.
+ * dsf_batch_norm_train      nn.BatchNorm1d on batch statistics, one launch: r = relu_in ? max(x, 0) : x (Prenet's ReLU, pe.py:14-18); mean and
+ *                           biased variance of every channel over the B * T live columns (padding frames count, the tail does not; centred
+ *                           two-pass variance); y = ((r - mean) rstd gamma + beta) keep[b][t] (keep may be NULL); save_mean / save_rstd [C];
+ *                           running_mean = (1 - m) running_mean + m mean, running_var = (1 - m) running_var + m var n / (n - 1) in place (either
+ *                           may be NULL).  B * T < 2 is DSD_ERR_INVALID (torch raises there too).
+ * dsf_batch_norm_train_bwd  one launch: dgamma, dbeta [C] and dx = gamma rstd (g - mean(g) - xhat mean(g xhat)), g = dy keep, times (x > 0) under
+ *                           relu_in.  x = the forward's input.
+ * dsf_group_norm_bwd        backward of dsf_group_norm (relu as there; the residual's gradient is dy itself): dx, dgamma, dbeta [C] in two
+ *                           launches; statistics and the ReLU mask are recomputed from x; workspace: dsf_group_norm_bwd_workspace_floats(B, C)
+ *                           floats (per-utterance partials, added in utterance order).  At most 64 channels per group.
+ * dsf_f0_loss               FastSpeech2Task.add_f0_loss (tasks/tts/fs2.py:254-269) with the caller's nonpadding mask (PitchExtractionTask:
+ *                           mel.abs().sum(-1) > 0): pitch_pred [B][T][channels] fp32 with element strides sb / st / sc; f0, uv, nonpadding [B][T]
+ *                           contiguous fp32 (uv may be NULL unless use_uv).  out[0] = sum(BCEWithLogits(p1, uv) np) / sum(np) lam_uv (0 without
+ *                           use_uv), out[1] = sum(|p0 - f0| np') / sum(np') lam_f0 (l2: the square), np' = np (uv == 0) under use_uv; out[2],
+ *                           out[3] = the two mask sums.  Two launches; workspace: dsf_f0_loss_workspace_floats() floats.
+ * dsf_f0_loss_bwd           one launch: d_pitch_pred [B][T][channels] contiguous = d/d pitch_pred of grad_out[0] out[0] + grad_out[1] out[1]
+ *                           (grad_out a DEVICE [2]); stats = the forward's out. */
+int dsf_batch_norm_train(const float* x, const float* gamma, const float* beta, const float* keep, float* y, float* save_mean, float* save_rstd,
+                         float* running_mean, float* running_var, int32_t B, int32_t C, int32_t T, float eps, float momentum, int32_t relu_in,
+                         void* stream);
+int dsf_batch_norm_train_bwd(const float* x, const float* save_mean, const float* save_rstd, const float* gamma, const float* dy, const float* keep,
+                             float* dx, float* dgamma, float* dbeta, int32_t B, int32_t C, int32_t T, int32_t relu_in, void* stream);
+int64_t dsf_group_norm_bwd_workspace_floats(int32_t B, int32_t C);
+int dsf_group_norm_bwd(const float* x, const float* gamma, const float* beta, const float* dy, float* dx, float* dgamma, float* dbeta,
+                       float* workspace, int32_t B, int32_t C, int32_t groups, int32_t T, float eps, int32_t relu, void* stream);
+int64_t dsf_f0_loss_workspace_floats(void);
+int dsf_f0_loss(const float* pitch_pred, int64_t sb, int64_t st, int64_t sc, const float* f0, const float* uv, const float* nonpadding, int32_t B,
+                int32_t T, int32_t channels, int32_t use_uv, int32_t l2, float lam_uv, float lam_f0, float* workspace, float* out, void* stream);
+int dsf_f0_loss_bwd(const float* pitch_pred, int64_t sb, int64_t st, int64_t sc, const float* f0, const float* uv, const float* nonpadding, int32_t B,
+                    int32_t T, int32_t channels, int32_t use_uv, int32_t l2, float lam_uv, float lam_f0, const float* stats, const float* grad_out,
+                    float* d_pitch_pred, void* stream);
 
 /* FastSpeech2 training objective (tasks/tts/fs2.py:111-283; usr/diffsinger_task.py:359-389, :443-473), forward and backward; no allocation, no
  * synchronisation, every sum in a fixed order (two evaluations are bitwise equal).  Workspaces: dsf_fs2_loss_workspace_floats(B, T, 0) floats for
