@@ -21,7 +21,7 @@ LIB = os.path.join(PKG, 'libdsdenoise.so')
 # -amdgpu-mfma-vgpr-form=1 (round 6): MFMA results in the ARCHITECTURAL register file wherever they fit.  hipcc's default for a kernel that may
 # use all 512 registers (one wave per SIMD) is the accumulation-register form - every accumulator the vector ALU touches afterwards (output
 # transform, gate, residual, epilogues) then crosses between the two files with v_accvgpr_read / _write, 8 cycles of matrix time each beside
-# fp32 MFMAs.  Same source, same results; A/B on one box (profiles/r6_09_*): k_loop 127.95 -> 126.19 ms, k_loop_wino 101.9 -> 101.0 ms (and its
+# fp32 MFMAs.  Same source, same results; A/B on one box (profiles/r6_09_*): k_loop 127.95 -> 126.19 ms, the Winograd loop 101.9 -> 101.0 ms (and its
 # 15 spilled dwords -> 8, k_loop's 43 -> 0), the training step 5.26 -> 5.17 ms, vocoder / FastSpeech2 unchanged.
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC', '-ffp-contract=off', '-mllvm', '-amdgpu-mfma-vgpr-form=1']
 

@@ -6,8 +6,8 @@
 #include "dsd_split.hpp"
 #include "dsd_loop_split.hpp"
 #include "dsd_loop_wino.hpp"
-#include "dsd_loop_wino_sa.hpp"
 #include "dsd_lat_wino.hpp"
+#include "dsd_path.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -281,9 +281,6 @@ extern "C" int dsd_create(const dsd_config* cfg, int device, dsd_handle** out) {
         (void)hipFuncSetAttribute((const void*)k_lat_conv_w<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLatConvWLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_lat_conv_w<4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLatConvWLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_lat_conv_w<8>, hipFuncAttributeMaxDynamicSharedMemorySize, kLatConvWLdsBytes);
-        // (k_loop_wino, the form k_loop_wino_sa replaced on this path, stays instantiated: tests/golden/kernel_isa_hashes.json lists its device code)
-        (void)hipFuncSetAttribute((const void*)k_loop_wino<HEAD_DDPM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopWinoLdsBytes);
-        (void)hipFuncSetAttribute((const void*)k_loop_wino<HEAD_PLMS, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopWinoLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_loop_wino_sa<HEAD_DDPM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopWinoLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_loop_wino_sa<HEAD_PLMS, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLoopWinoLdsBytes);
         (void)hipFuncSetAttribute((const void*)k_head<HEAD_EPS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kHeadLdsBytes);
@@ -330,30 +327,12 @@ extern "C" int dsd_set_layer_tile(dsd_handle* h, int32_t frames) {
 
 extern "C" int64_t dsd_device_bytes(dsd_handle* h) { return h ? h->bytes + h->bytes_ws : 0; }
 
-// Row split G of the latency kernels for the prepared batch, 0 = not on that path.  Automatic mode: the largest G in {16, 8, 4, 2} that
-// still gives every workgroup a CU of its own - i.e. batches that leave at least half of the chip idle - and G = 8 for the band above it
-// (between half and 5/8 of the CU count in tiles: 129-160 on 256 CUs, e.g. ONE phrase of 4200-5000 frames or 5 x 1024): the persistent loop
-// leaves 37-50 % of the CUs without a tile there, 8 x ntiles workgroups in at most five grid waves measured 115-121 ms against its 127 ms
-// per K = 100 call (profiles/r47_midsize_paths.jsonl); one more grid wave (163 tiles) and the loop wins again.
-static int lat_g(const dsd_handle* h) {
-    if (h->split_mode || h->layer_tile_req || h->lat_req == 0 || h->loop_mode < 2) return 0;
-    int g = (16 * h->ntiles <= h->n_cu) ? 16 : (8 * h->ntiles <= h->n_cu) ? 8 : (4 * h->ntiles <= h->n_cu) ? 4 : (2 * h->ntiles <= h->n_cu) ? 2 : 0;
-    // (the band exists for the DIRECT-convolution loop only: the Winograd loop takes 104 ms per launch and wins it back - profiles/r5_03_shape_sweep.jsonl)
-    if (g == 0 && h->loop_mode == 2 && !(h->conv_mode == 1 && h->w1w) && h->ntiles < h->n_cu && 8 * h->ntiles <= 5 * h->n_cu) g = 8;
-    if (h->loop_mode == 3 && g == 0) g = 2;
-    if (g && (h->lat_req == 2 || h->lat_req == 4 || h->lat_req == 8 || h->lat_req == 16)) g = h->lat_req;
-    return g;
+// The path decision for the prepared batch (dsd_path.hpp): every launch site and getter below reads this one result.
+static SamplerPath path_of(const dsd_handle* h) {
+    return sampler_path(PathInput{h->n_cu, h->B, h->ntile32, h->L, h->loop_mode, h->lat_req, h->layer_tile_req, h->conv_mode, h->w1w != nullptr,
+                                  h->split_mode, h->use_graph, h->persist_off});
 }
-
-static int layer_nb(const dsd_handle* h) {
-    if (h->split_mode) return 1;               // the split-precision layer kernel exists for 32-frame tiles only
-    if (lat_g(h)) return 1;
-    if (h->layer_tile_req) return h->layer_tile_req / 32;
-    // 32-frame workgroups until there are enough of them to keep two resident per CU on all 256 CUs; beyond
-    // that 64-frame workgroups halve the weight traffic out of L2 per frame.
-    return (h->ntiles > 1024) ? 2 : 1;
-}
-extern "C" int dsd_get_layer_tile(dsd_handle* h) { return h ? 32 * layer_nb(h) : 0; }
+extern "C" int dsd_get_layer_tile(dsd_handle* h) { return h ? path_of(h).layer_frames : 0; }
 
 // Function attributes (dynamic LDS above 64 KiB) belong to a DEVICE's code object: true the first time call site `site` is reached on the
 // current device - a process that drives several GPUs (the reference's DP threads, utils/pl_utils.py:146-154) sets them on each.
@@ -611,8 +590,6 @@ extern "C" int dsd_set_spec_range(dsd_handle* h, const float* spec_min, const fl
 // ------------------------------------------------------------------------------------------------------------
 // prepare: workspace + hoisted conditioner projection
 // ------------------------------------------------------------------------------------------------------------
-static bool wino_applicable(const dsd_handle* h);
-
 // cp[l] = Wc_l cond + bc_l + bd_l of the prepared batch (condT stays in the workspace), in the 32x32 fragment order every per-layer / latency
 // kernel and k_loop read - or in the accumulator order of the Winograd loop (dsd_loop_wino.hpp)
 static int launch_condproj(dsd_handle* h, bool wino, hipStream_t s) {
@@ -676,7 +653,7 @@ extern "C" int dsd_prepare(dsd_handle* h, int32_t B, int32_t T, const float* con
     HIP_TRY(hipGetLastError());
     h->prepared = true;
     // the hoisted conditioner projection in the accumulator order of the path this batch will take (a later switch of path re-lays it: ensure_cp)
-    return launch_condproj(h, wino_applicable(h), s);
+    return launch_condproj(h, path_of(h).kind == PathKind::PersistentWino, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -692,16 +669,16 @@ static int launch_inproj(dsd_handle* h, const float* spec, hipStream_t s) {
 template <int G>
 static void launch_lat(const LatParams& p, hipStream_t s) {
     const dim3 grid((unsigned)lat_grid(p.ntiles, G));
-    bool wino = false;
-    if constexpr (G != 16) {
-        if (p.w1w) { hipLaunchKernelGGL((k_lat_conv_w<G>), grid, dim3(kThreads), kLatConvWLdsBytes, s, p); wino = true; }      // Winograd F(2,3) convolution
-    }
-    if (!wino) hipLaunchKernelGGL((k_lat_conv<G>), grid, dim3(kThreads), kLatConvLdsBytes, s, p);
+    // p.w1w is set where the path's convolution node is the Winograd F(2,3) form (SamplerPath::lat_wino: never at G = 16)
+    if constexpr (G == 16) hipLaunchKernelGGL((k_lat_conv<G>), grid, dim3(kThreads), kLatConvLdsBytes, s, p);
+    else if (p.w1w) hipLaunchKernelGGL((k_lat_conv_w<G>), grid, dim3(kThreads), kLatConvWLdsBytes, s, p);
+    else hipLaunchKernelGGL((k_lat_conv<G>), grid, dim3(kThreads), kLatConvLdsBytes, s, p);
     hipLaunchKernelGGL((k_lat_out<G>), grid, dim3(kThreads), kLatOutLdsBytes, s, p);
 }
 
 static int launch_layer(dsd_handle* h, int l, int t_uniform, const int* t_dev, hipStream_t s, unsigned long long* dbg = nullptr) {
-    if (const int G = lat_g(h)) {
+    const SamplerPath path = path_of(h);
+    if (const int G = path.G) {
         // latency mode (dsd_lat.hpp): the layer as two kernels whose workgroups split the output rows of a tile G ways
         LatParams q{};
         q.x_in = (l & 1) ? h->xb : h->xa;
@@ -717,14 +694,12 @@ static int launch_layer(dsd_handle* h, int l, int t_uniform, const int* t_dev, h
         q.t_dev = t_dev; q.t_uniform = t_uniform; q.ds_tstride = h->L * kC;
         q.T = h->T; q.ntile32 = h->ntile32; q.ntiles = h->ntiles; q.dil = h->dil[l];
         q.first = (l == 0); q.last = (l == h->L - 1);
-        // the Winograd form of the convolution for G = 2 / 4 / 8 (4 x 777: 71.0 ms against 81.9, 1 x 1550: 45.3 against 50.2, 1 x 1000: 31.2 against 32.0);
-        // at G = 16 a wave's share is 128 short MFMAs and the direct kernel with its own packing stays ahead (24.6 ms against 25.0; profiles/r5_11_*)
-        q.w1w = (h->conv_mode == 1 && h->w1w && G != 16) ? h->w1w + (size_t)l * kWnSteps * (kWnStepBytes / 16) : nullptr;
+        q.w1w = path.lat_wino ? h->w1w + (size_t)l * kWnSteps * (kWnStepBytes / 16) : nullptr;
         if (G == 16) launch_lat<16>(q, s); else if (G == 8) launch_lat<8>(q, s); else if (G == 4) launch_lat<4>(q, s); else launch_lat<2>(q, s);
         HIP_TRY(hipGetLastError());
         return DSD_OK;
     }
-    const int nb = layer_nb(h);
+    const int nb = path.layer_frames / 32;
     LayerParams p{};
     p.x_in = (l & 1) ? h->xb : h->xa;
     p.x_out = (l & 1) ? h->xa : h->xb;
@@ -784,7 +759,7 @@ static HeadParams head_base(dsd_handle* h) {
 
 template <int MODE>
 static int launch_head(dsd_handle* h, const HeadParams& p, bool fuse, hipStream_t s) {
-    if (MODE != HEAD_EPS && lat_g(h) >= 8) {
+    if (MODE != HEAD_EPS && path_of(h).G >= 8) {
         // G = 8 latency path: the head row-split like the layers (dsd_lat.hpp): skip projection on 8 workgroups per tile -> final projection +
         // sampler update on 3 of the 4 workgroups per tile of its grid (lat_grid(ntiles, 4); the fourth returns) -> next input projection on 8.  hbuf = the gate buffer (free behind the last layer), pbuf = the x buffer
         // the last layer read (the other one receives the next x)
@@ -883,24 +858,6 @@ extern "C" int dsd_denorm_spec(dsd_handle* h, const float* x, const float* mask,
 // ------------------------------------------------------------------------------------------------------------
 // sampling loops
 // ------------------------------------------------------------------------------------------------------------
-// Enqueue the whole DDPM loop on stream s, operating on the internal spec buffer h->xs.
-static int enqueue_ddpm(dsd_handle* h, int k_step, hipStream_t s) {
-    const size_t bmt = (size_t)h->B * h->M * h->T;
-    DSD_TRY(launch_inproj(h, h->xs, s));
-    for (int j = 0; j < k_step; ++j) {
-        const int t = k_step - 1 - j;
-        DSD_TRY(launch_stack(h, t, nullptr, s));
-        HeadParams p = head_base(h);
-        p.x_base = h->xs; p.x_out = h->xs;
-        p.noise_off = (size_t)j * bmt; p.step_id = (unsigned)j;
-        p.sa = h->tab[6][t]; p.sb = h->tab[7][t]; p.c1 = h->tab[10][t]; p.c2 = h->tab[11][t];
-        // nonzero_mask * exp(0.5 * logvar): fp32 like the reference's [B,1,1,1] tensors (:165-166)
-        p.sigma = (t == 0) ? 0.f : std::exp(0.5f * h->tab[9][t]);
-        DSD_TRY(launch_head<HEAD_DDPM>(h, p, /*fuse next in-proj*/ t > 0, s));
-    }
-    return DSD_OK;
-}
-
 // get_x_pred coefficients (shallow_diffusion_tts.py:174-185), in fp32 like the reference
 static void plms_coef(const dsd_handle* h, int t, int interval, float* dA, float* cx, float* ce) {
     const float a_t = h->tab[1][t];
@@ -911,47 +868,9 @@ static void plms_coef(const dsd_handle* h, int t, int interval, float* dA, float
     *ce = 1.0f / (a_t_sq * (std::sqrt((1.0f - a_prev) * a_t) + std::sqrt((1.0f - a_t) * a_prev)));
 }
 
-static int enqueue_plms(dsd_handle* h, int k_step, int interval, hipStream_t s) {
-    DSD_TRY(launch_inproj(h, h->xs, s));
-    int hist = 0;           // len(noise_list), capped at 3 for the formula choice
-    int head_slot = 0;      // ring slot receiving the next stored eps
-    std::vector<int> ts;
-    for (int i = 0; i < k_step; i += interval) ts.push_back(i);
-    for (int n = (int)ts.size() - 1; n >= 0; --n) {
-        const int t = ts[n];
-        const bool more = n > 0;
-        float dA, cx, ce;
-        plms_coef(h, t, interval, &dA, &cx, &ce);
-        DSD_TRY(launch_stack(h, t, nullptr, s));
-        HeadParams p = head_base(h);
-        p.dA = dA; p.cx = cx; p.ce = ce;
-        float* slot = h->ering[head_slot & 3];
-        if (hist == 0) {
-            // warm-up (:188-192): x_pred from the raw eps, second evaluation at max(t - interval, 0)
-            p.order = PLMS_RAW; p.x_base = h->xs; p.x_out = h->xtmp; p.eps_out = slot;
-            DSD_TRY(launch_head<HEAD_PLMS>(h, p, true, s));
-            const int t_prev = std::max(t - interval, 0);
-            DSD_TRY(launch_stack(h, t_prev, nullptr, s));
-            HeadParams q = head_base(h);
-            q.dA = dA; q.cx = cx; q.ce = ce;
-            q.order = PLMS_HEUN; q.x_base = h->xs; q.x_out = h->xs; q.eps_out = nullptr; q.e1 = slot;
-            DSD_TRY(launch_head<HEAD_PLMS>(h, q, more, s));
-        } else {
-            p.order = (hist == 1) ? PLMS_AB2 : (hist == 2) ? PLMS_AB3 : PLMS_AB4;
-            p.x_base = h->xs; p.x_out = h->xs; p.eps_out = slot;
-            p.e1 = h->ering[(head_slot - 1) & 3]; p.e2 = h->ering[(head_slot - 2) & 3]; p.e3 = h->ering[(head_slot - 3) & 3];
-            DSD_TRY(launch_head<HEAD_PLMS>(h, p, more, s));
-        }
-        ++head_slot;
-        hist = std::min(hist + 1, 3);
-    }
-    return DSD_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// persistent loop (dsd_loop.hpp)
-// ------------------------------------------------------------------------------------------------------------
-// The per-evaluation head parameters, exactly what enqueue_ddpm / enqueue_plms bake into their launches.
+// The evaluation schedule of a sampling loop: for (kind 0 DDPM / 1 PLMS, k_step, interval) the head parameters and the step index of every
+// denoiser evaluation, in order.  The only place that makes it: the per-layer launches (enqueue_evals) bake it into their arguments, the
+// persistent loops read it from the device (get_plan).
 static void plan_evals(dsd_handle* h, int kind, int k_step, int interval, std::vector<HeadParams>& ev, std::vector<int>& ts_out) {
     const size_t bmt = (size_t)h->B * h->M * h->T;
     if (kind == 0) {
@@ -961,12 +880,14 @@ static void plan_evals(dsd_handle* h, int kind, int k_step, int interval, std::v
             p.x_base = h->xs; p.x_out = h->xs;
             p.noise_off = (size_t)j * bmt; p.step_id = (unsigned)j;
             p.sa = h->tab[6][t]; p.sb = h->tab[7][t]; p.c1 = h->tab[10][t]; p.c2 = h->tab[11][t];
+            // nonzero_mask * exp(0.5 * logvar): fp32 like the reference's [B,1,1,1] tensors (:165-166)
             p.sigma = (t == 0) ? 0.f : std::exp(0.5f * h->tab[9][t]);
             ev.push_back(p); ts_out.push_back(t);
         }
         return;
     }
-    int hist = 0, head_slot = 0;
+    int hist = 0;           // len(noise_list), capped at 3 for the formula choice
+    int head_slot = 0;      // ring slot receiving the next stored eps
     std::vector<int> ts;
     for (int i = 0; i < k_step; i += interval) ts.push_back(i);
     for (int n = (int)ts.size() - 1; n >= 0; --n) {
@@ -977,6 +898,7 @@ static void plan_evals(dsd_handle* h, int kind, int k_step, int interval, std::v
         p.dA = dA; p.cx = cx; p.ce = ce;
         float* slot = h->ering[head_slot & 3];
         if (hist == 0) {
+            // warm-up (:188-192): x_pred from the raw eps, second evaluation at max(t - interval, 0)
             p.order = PLMS_RAW; p.x_base = h->xs; p.x_out = h->xtmp; p.eps_out = slot;
             ev.push_back(p); ts_out.push_back(t);
             HeadParams q = head_base(h);
@@ -994,6 +916,27 @@ static void plan_evals(dsd_handle* h, int kind, int k_step, int interval, std::v
     }
 }
 
+// Enqueue a whole sampling loop as per-layer kernels on stream s, operating on the internal spec buffer h->xs: the L layers and the head of
+// every evaluation of the schedule; every head but the last also makes the next evaluation's input projection.
+template <int MODE>
+static int enqueue_evals(dsd_handle* h, const std::vector<HeadParams>& ev, const std::vector<int>& ts, hipStream_t s) {
+    DSD_TRY(launch_inproj(h, h->xs, s));
+    const int n = (int)ev.size();
+    for (int i = 0; i < n; ++i) {
+        DSD_TRY(launch_stack(h, ts[i], nullptr, s));
+        DSD_TRY(launch_head<MODE>(h, ev[i], /*fuse next in-proj*/ i + 1 < n, s));
+    }
+    return DSD_OK;
+}
+static int enqueue_loop(dsd_handle* h, int kind, int k_step, int interval, hipStream_t s) {
+    std::vector<HeadParams> ev; std::vector<int> ts;
+    plan_evals(h, kind, k_step, interval, ev, ts);
+    return kind == 0 ? enqueue_evals<HEAD_DDPM>(h, ev, ts, s) : enqueue_evals<HEAD_PLMS>(h, ev, ts, s);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// persistent loop (dsd_loop.hpp)
+// ------------------------------------------------------------------------------------------------------------
 // ONE persistent loop at a time per device: all workgroups of a k_loop launch wait for each other, so two such launches on two
 // streams of one GPU (two handles = two models of one process, or one handle driven from two streams) could each hold part of the
 // CUs and starve the other into its timeout.  Every persistent launch therefore waits (on the device, hipStreamWaitEvent) for the
@@ -1005,31 +948,9 @@ static hipEvent_t g_loop_ev[kMaxDevices];
 static hipStream_t g_loop_stream[kMaxDevices];
 static bool g_loop_has[kMaxDevices];
 
-// true when the prepared batch can run as the persistent loop: 32-frame tiles, a whole utterance fits the co-resident grid
-static bool loop_applicable(const dsd_handle* h) {
-    if (!((h->loop_mode == 1 || h->loop_mode == 2) && !h->persist_off && h->use_graph && layer_nb(h) == 1 && h->n_cu >= 8 &&
-          h->ntile32 <= h->n_cu && h->L <= kLoopMaxLayers)) return false;
-    if (h->loop_mode == 2) {
-        if (lat_g(h)) return false;
-        // chunks of whole utterances may leave much of the chip idle (T = 5000: 157 tiles per launch on 256 CUs); the per-layer kernels
-        // have no such constraint, only the wave quantisation of their grid, and cost ~5 % more at equal occupancy
-        const int upc = std::max(1, h->n_cu / h->ntile32), chunks = (h->B + upc - 1) / upc;
-        const double u_p = (double)h->ntiles / ((double)chunks * h->n_cu);
-        // (the per-layer kernels evaluate the direct convolution: at equal occupancy they take 1.05 x the direct loop's time and 1.29 x the
-        // Winograd loop's - 133 ms against 127 / 103.7 ms per 256 tiles)
-        const double rel = (h->conv_mode == 1 && h->w1w && !h->split_mode) ? 0.78 : 0.95;
-        const double u_l = rel * (double)h->ntiles / ((double)((h->ntiles + h->n_cu - 1) / h->n_cu) * h->n_cu);
-        if (u_l > u_p) return false;
-    }
-    return true;
-}
-
-// the prepared batch takes the persistent loop AND that loop evaluates the dilated convolution as Winograd F(2,3) (dsd_loop_wino.hpp)
-static bool wino_applicable(const dsd_handle* h) { return h->conv_mode == 1 && !h->split_mode && h->w1w && loop_applicable(h); }
-
 static int get_plan(dsd_handle* h, int kind, int k_step, int interval, dsd_handle::LoopPlan** out);
 
-static int run_persistent(dsd_handle* h, int kind, int k_step, int interval, hipStream_t s) {
+static int run_persistent(dsd_handle* h, const SamplerPath& path, int kind, int k_step, int interval, hipStream_t s) {
     dsd_handle::LoopPlan* plan = nullptr;
     DSD_TRY(get_plan(h, kind, k_step, interval, &plan));
     if (h->loop_cap_tiles < h->ntiles) {
@@ -1040,7 +961,7 @@ static int run_persistent(dsd_handle* h, int kind, int k_step, int interval, hip
         h->loop_cap_tiles = h->ntiles;
     }
     HIP_TRY(hipMemsetAsync(h->loop_flags, 0, ((size_t)h->ntiles + 64) * sizeof(unsigned), s));
-    const bool wino = wino_applicable(h);
+    const bool wino = path.kind == PathKind::PersistentWino;
     DSD_TRY(ensure_cp(h, wino, s));
     LoopParams p{};
     p.w1p = h->w1p; p.w2p = h->w2p; p.b2raw = h->b2raw; p.cp = h->cp; p.cp_lstride = (size_t)h->ntiles * 4096;
@@ -1053,8 +974,6 @@ static int run_persistent(dsd_handle* h, int kind, int k_step, int interval, hip
     p.flags = h->loop_flags; p.halo = h->loop_halo; p.tmo = h->loop_flags + h->ntiles;
     h->loop_tmo_at = h->ntiles;
     p.dbg = h->loop_dbg; p.dbg_phase = h->loop_dbg_phase;
-    // chunks of whole utterances, at most one workgroup per CU (all workgroups of a launch wait for each other)
-    const int utt_per_chunk = std::max(1, h->n_cu / h->ntile32);
     const int dv = (h->device >= 0 && h->device < kMaxDevices) ? h->device : 0;
     std::lock_guard<std::mutex> guard(g_loop_mu[dv]);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1064,10 +983,10 @@ static int run_persistent(dsd_handle* h, int kind, int k_step, int interval, hip
         if (!g_loop_ev[dv]) HIP_TRY(hipEventCreateWithFlags(&g_loop_ev[dv], hipEventDisableTiming));
         if (g_loop_has[dv] && g_loop_stream[dv] != s) HIP_TRY(hipStreamWaitEvent(s, g_loop_ev[dv], 0));
     }
-    for (int b0 = 0; b0 < h->B; b0 += utt_per_chunk) {
-        const int nb = std::min(utt_per_chunk, h->B - b0);
+    for (int b0 = 0; b0 < h->B; b0 += path.utt_per_chunk) {
+        const int nb = std::min(path.utt_per_chunk, h->B - b0);
         p.tile_base = b0 * h->ntile32; p.n_tiles = nb * h->ntile32;
-        if (h->split_mode) {
+        if (path.kind == PathKind::PersistentSplit) {
             // EXPERIMENT (dsd_loop_split.hpp): the same loop with the layers' contractions as six bf16 plane products per fp32 product
             const LoopSplitParams q = h->split_w == 2 ? LoopSplitParams{p, h->wl2, h->wl2 + (size_t)48 * 4 * 512, (unsigned)((size_t)h->L * 64 * 4 * 8192), h->split_touch}
                                                         : LoopSplitParams{p, h->wlc, h->wlc + (size_t)48 * 4 * 768, (unsigned)((size_t)h->L * 64 * 4 * 12288), h->split_touch};
@@ -1078,7 +997,7 @@ static int run_persistent(dsd_handle* h, int kind, int k_step, int interval, hip
             else DSD_LAUNCH_SPLIT(0);
 #undef DSD_LAUNCH_SPLIT
         } else if (wino) {
-            // Winograd F(2,3) form of the dilated convolution (dsd_loop_wino.hpp; k_loop_wino_sa, dsd_loop_wino_sa.hpp): the default of this path
+            // Winograd F(2,3) form of the dilated convolution (k_loop_wino_sa, dsd_loop_wino.hpp): the default of this path
             const LoopWinoParams q{p, h->w1w, (unsigned)((size_t)h->L * kWnSteps * kWnStepBytes), h->wino_touch};
             const dim3 grid((unsigned)p.n_tiles), block(kThreads);
             if (kind == 0) hipLaunchKernelGGL((k_loop_wino_sa<HEAD_DDPM, 4>), grid, block, kLoopWinoLdsBytes, s, q);
@@ -1125,19 +1044,20 @@ static int run_loop(dsd_handle* h, int kind, float* x, const float* noise, int k
         if (!noise) hipLaunchKernelGGL(k_set_seed, dim3(1), dim3(1), 0, s, h->seed_cell, h->noise_seed);
         HIP_TRY(hipGetLastError());
     }
-    if (loop_applicable(h)) {
-        DSD_TRY(run_persistent(h, kind, k_step, interval, s));
+    const SamplerPath path = path_of(h);
+    if (path.persistent()) {
+        DSD_TRY(run_persistent(h, path, kind, k_step, interval, s));
     } else if (!h->use_graph) {
         DSD_TRY(ensure_cp(h, false, s));
-        DSD_TRY(kind == 0 ? enqueue_ddpm(h, k_step, s) : enqueue_plms(h, k_step, interval, s));
+        DSD_TRY(enqueue_loop(h, kind, k_step, interval, s));
     } else {
         DSD_TRY(ensure_cp(h, false, s));
-        const GraphKey key{kind, h->B, h->T, k_step, interval, layer_nb(h) + 100 * lat_g(h) + 10000 * ((h->conv_mode == 1 && h->w1w) ? 1 : 0)};      // (the latency nodes differ by convolution form)
+        const GraphKey key{kind, h->B, h->T, k_step, interval, path.graph_tile};
         auto it = h->graphs.find(key);
         if (it == h->graphs.end()) {
             hipGraph_t g = nullptr;
             HIP_TRY(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-            const int rc = (kind == 0) ? enqueue_ddpm(h, k_step, h->cap_stream) : enqueue_plms(h, k_step, interval, h->cap_stream);
+            const int rc = enqueue_loop(h, kind, k_step, interval, h->cap_stream);
             const hipError_t e = hipStreamEndCapture(h->cap_stream, &g);
             if (rc != DSD_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
             if (e != hipSuccess) return fail(DSD_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
@@ -1278,7 +1198,7 @@ extern "C" int dsd_set_lat_split(dsd_handle* h, int32_t g) {
     return DSD_OK;
 }
 
-extern "C" int dsd_get_lat_split(dsd_handle* h) { return (h && h->prepared) ? lat_g(h) : 0; }
+extern "C" int dsd_get_lat_split(dsd_handle* h) { return (h && h->prepared) ? path_of(h).G : 0; }
 
 extern "C" int dsd_set_conv_mode(dsd_handle* h, int32_t mode, int32_t touch_ahead) {
     if (!h || mode < 0 || mode > 1) return fail(DSD_ERR_INVALID, "dsd_set_conv_mode: mode must be 0 (direct K = 768 contraction) or 1 (Winograd F(2,3))");
@@ -1288,22 +1208,13 @@ extern "C" int dsd_set_conv_mode(dsd_handle* h, int32_t mode, int32_t touch_ahea
     return DSD_OK;
 }
 
-// 1 when the dilated convolution of the prepared batch runs as Winograd F(2,3): the persistent loop k_loop_wino, or the conv node of the
-// row-split latency kernels at G = 2 / 4 / 8 (k_lat_conv_w, launch_layer); 0: the direct form (mode 0, G = 16, per-layer kernels, split mode)
-extern "C" int dsd_get_conv_mode(dsd_handle* h) {
-    if (!h || !h->prepared) return 0;
-    if (wino_applicable(h)) return 1;
-    const int g = loop_applicable(h) ? 0 : lat_g(h);
-    return (h->conv_mode == 1 && h->w1w && !h->split_mode && (g == 2 || g == 4 || g == 8)) ? 1 : 0;
-}
+// 1 when the dilated convolution of the prepared batch runs as Winograd F(2,3): the persistent loop k_loop_wino_sa, or the conv node of the
+// row-split latency kernels at G = 2 / 4 / 8 (k_lat_conv_w); 0: the direct form (mode 0, G = 16, per-layer kernels, split mode)
+extern "C" int dsd_get_conv_mode(dsd_handle* h) { return (h && h->prepared && path_of(h).winograd()) ? 1 : 0; }
 
-extern "C" int dsd_get_loop_mode(dsd_handle* h) { return (h && h->prepared && loop_applicable(h)) ? 1 : 0; }
+extern "C" int dsd_get_loop_mode(dsd_handle* h) { return (h && h->prepared && path_of(h).persistent()) ? 1 : 0; }
 
-extern "C" int dsd_loop_launches(dsd_handle* h) {
-    if (!h || !h->prepared || !loop_applicable(h)) return 0;
-    const int utt_per_chunk = std::max(1, h->n_cu / h->ntile32);
-    return (h->B + utt_per_chunk - 1) / utt_per_chunk;
-}
+extern "C" int dsd_loop_launches(dsd_handle* h) { return (h && h->prepared) ? path_of(h).launches : 0; }
 
 extern "C" int dsd_loop_timeouts(dsd_handle* h, void* stream) {
     if (!h) return fail(DSD_ERR_INVALID, "dsd_loop_timeouts: null handle");
@@ -1349,7 +1260,7 @@ extern "C" int dsd_debug_loop_timeline(dsd_handle* h, float* x, const float* noi
                                        int32_t max_wg, int32_t* n_wg, void* stream) {
     DSD_TRY(check_ready(h, "dsd_debug_loop_timeline", true));
     if (!x || !noise || !out || !n_wg) return fail(DSD_ERR_INVALID, "dsd_debug_loop_timeline: null argument");
-    if (!loop_applicable(h)) return fail(DSD_ERR_STATE, "dsd_debug_loop_timeline: the prepared batch does not take a persistent path");
+    if (!path_of(h).persistent()) return fail(DSD_ERR_STATE, "dsd_debug_loop_timeline: the prepared batch does not take a persistent path");
     if (k_step < 2 || phase / h->L >= k_step - 1) return fail(DSD_ERR_INVALID, "dsd_debug_loop_timeline: pick a phase of an evaluation that is not the last");
     const int nwg = h->ntiles;                   // one stamp block per workgroup = per tile
     if (h->ntiles > h->n_cu || nwg > max_wg) return fail(DSD_ERR_INVALID, "dsd_debug_loop_timeline: needs a single-launch batch (%d workgroups)", nwg);
@@ -1493,7 +1404,7 @@ extern "C" int dsd_debug_layer_timeline(dsd_handle* h, int32_t layer, int32_t t,
     hipStream_t s = (hipStream_t)stream;
     DSD_TRY(build_step_table(h, t + 1, s));
     DSD_TRY(ensure_cp(h, false, s));
-    const int nb = layer_nb(h);
+    const int nb = path_of(h).layer_frames / 32;
     const int blocks = h->B * ((h->ntile32 + nb - 1) / nb);
     if (blocks > max_blocks) return fail(DSD_ERR_INVALID, "dsd_debug_layer_timeline: %d blocks > buffer %d", blocks, max_blocks);
     unsigned long long* d = nullptr;

@@ -27,12 +27,12 @@
 //   * the halo buffers are [side][8 frames][256 channels]; a tile's first / last 8 frames are held by the lanes j < 8 / j >= 24.
 #pragma once
 #include "dsd_kernels.hpp"
+#include "dsd_path.hpp"      // kLoopMaxLayers
 
 namespace dsd {
 
 typedef __attribute__((address_space(1))) unsigned gu32;
 
-constexpr int kLoopMaxLayers = 64;
 constexpr int kLoopSpinLimit = 1 << 21;     // ~2-4 s of polling: far beyond any legitimate skew, still bounded
 
 struct LoopParams {

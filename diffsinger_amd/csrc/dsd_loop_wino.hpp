@@ -1,6 +1,8 @@
 // dsd_loop_wino.hpp - the persistent K-step loop of dsd_loop.hpp with the 3-tap dilated convolution (usr/diff/net.py:61,71: nn.Conv1d(C, 2C, 3,
 // padding=dilation, dilation=dilation)) evaluated as WINOGRAD F(2,3) along the frame axis: fp32 in, fp32 out, exact-fp32 MFMA - the same dtype as
-// the reference, 2/3 of the convolution's multiplications.
+// the reference, 2/3 of the convolution's multiplications.  The kernel is k_loop_wino_sa, what the persistent path launches by default; the
+// constants, the pair-order helpers, k_pack_wino, L2TouchP, WinoPipe and LoopWinoParams in front of it are shared with the other Winograd
+// kernels (k_lat_conv_w, k_tr_stack_fwd_w, k_trb_fused_w).
 //
 // For an output pair (t, t + d) of a layer with dilation d, inputs d0 = y[t-d], d1 = y[t], d2 = y[t+d], d3 = y[t+2d] and taps g0, g1, g2
 // (out[t] = g0 y[t-d] + g1 y[t] + g2 y[t+d]):
@@ -11,8 +13,8 @@
 // add per B operand, made in registers from the frame-major y tile when the fragment is read; the output transform is register arithmetic
 // between the two halves of the contraction.
 //
-// How it maps onto the loop (everything not named here IS k_loop: tile ownership, x / skip sum in registers, halo exchange, out-projection,
-// head, sampler update, failure protocol):
+// How it maps onto the loop (everything not named here IS k_loop: tile ownership, x in registers, halo exchange, head, sampler update,
+// failure protocol):
 //   * a 32-frame tile splits into 32 / (2 d) blocks of d pairs for every d in {1, 2, 4, 8}: always 16 pairs p = blk * d + i <-> frames
 //     tE = 2 d blk + i and tO = tE + d.  The y tile is kept in PAIR order - E[p] = y[tE(p)], O[p] = y[tO(p)] - so that the four operands of
 //     pair p are rows E[p], O[p], O[p - d] (= y[tE - d]) and E[p + d] (= y[tO + d]): consecutive lanes read consecutive rows, and the
@@ -29,8 +31,18 @@
 //     (L2Touch, dsd_loop_split.hpp); eight register stages of 4 KiB per wave.
 //   * the hoisted conditioner projection is written by k_condproj as the INITIAL VALUES of the two accumulator sets, in this kernel's
 //     accumulator order (CondProjParams::wino), and fetched into them while they are dead: under the previous layer's out-projection.
+//   * the 32x32x2 pipes (out-projection, head, input projection) walk their chunks with compile-time bounds, fully unrolled
+//     (GemmPipe::run_static / run_bounded): across the back edge of GemmPipe::run hipcc copied the whole accumulator set every six chunks
+//     (tests/test_wino_acc_copies.py);
+//   * the skip row blocks of the out-projection ARE the running skip sum: the MFMA's C/D operand lives across the layers, an evaluation
+//     starts it from zero, the head reads it - no registers for the sum beside them, no add and no select behind the contraction.  The skip
+//     products therefore accumulate onto the running sum s (not s + (a sum started from 0));
+//   * the residual row blocks start from their bias (loaded in front of the gate) instead of zero: the residual products accumulate onto the
+//     bias b (not (a sum started from 0) + b);
+//   * the y tile is staged with the plain packed add wherever tile and halo lie inside the utterance.
 // Results differ from the direct form by reduction order and the transforms' roundings (tests/test_gpu_wino.py: within 2e-5 of k_loop on a
 // K = 100 loop, the oracle parity budget of 1e-4 holds with a 10 x margin); k_loop stays the bit-identity anchor of the per-layer kernels.
+// (The benchmark and the evidence files under profiles/ label this loop 'k_loop_wino<1, 4>'.)
 #pragma once
 #include "dsd_loop.hpp"
 #include "dsd_loop_split.hpp"
@@ -277,8 +289,34 @@ struct LoopWinoParams {
     int touch_ahead;            // steps the L2 touch runs in front (0 = off)
 };
 
+// fm_add_masked where nothing can be masked: two packed adds
+__device__ __forceinline__ float4 fm_add(const float4& x, const float4& d) {
+    typedef float f32x2_ __attribute__((ext_vector_type(2)));
+    const f32x2_ lo = f32x2_{x.x, x.y} + f32x2_{d.x, d.y}, hi = f32x2_{x.z, x.w} + f32x2_{d.z, d.w};
+    return make_float4(lo[0], lo[1], hi[0], hi[1]);
+}
+
+// inproj_tile (dsd_kernels.hpp: the same loads, the same order of arithmetic) with the K walk unrolled: no accumulator copies at a back edge
+__device__ __forceinline__ void inproj_tile_nb(const float* ptile, const float4* __restrict__ winp, const float4* __restrict__ binp, int nk,
+                                               float* __restrict__ xo_tile, int w, int lane) {
+    const int j = lane & 31, h = lane >> 5;
+    f32x16 acc[2][1];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) set4(acc[mb][0], q, binp[((w * 2 + mb) * 2 + h) * 4 + q]);
+    GemmPipe<2, 1, 32, 128, 6, TileB> pipe(winp + (size_t)w * nk * 128, lane, nk, TileB{ptile + 4 * h * 32 + j, 8 * 32, nk});
+    pipe.start();
+    pipe.template run_bounded<kMPad / 8>(acc, nk);
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            xo_tile[(64 * w + 32 * mb + frag_row(r, h)) * 32 + j] = fmaxf(acc[mb][0][r], 0.f);
+}
+
 template <int MODE, int S>
-__global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams pw) {
+__global__ __launch_bounds__(kThreads, 1) void k_loop_wino_sa(const LoopWinoParams pw) {
     constexpr int LDK = kFmLDK;
     const LoopParams& p = pw.lp;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -315,16 +353,22 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
     const bool has_left = tn > 0, has_right = tn + 1 < p.ntile32;
     const int M = p.head.M, T = p.T;
     const bool in_t = t0 + j < T;           // this lane's frame is a frame of the utterance
+    // Only the tile that contains frame T can mask anything: the workgroups whose tile (own frames / left halo / right halo) lies entirely
+    // inside the utterance stage y with the plain packed add, the others select per element (workgroup-uniform flags, made once per launch)
+    const bool own_cut = t0 + 32 > T, left_cut = t0 > T, right_cut = t0 + 32 + kHalo > T;
 
     float4 xq[2][4];        // x tile in fragment order: xq[mb][q] = channels 64 w + 32 mb + 8 q + 4 h + {0,1,2,3} of frame j
-    float4 skp[2][4];       // running skip sum of this wave's skip rows, the same order
+    // The out-projection's accumulators, row blocks 0, 1 residual and 2, 3 skip.  The skip row blocks ARE the running skip sum: they live across
+    // the layers, every layer's out-projection accumulates its products onto them (the MFMA's C/D operand), an evaluation starts them from
+    // zero and the head reads them - no second set of registers for the sum, no add and no select behind the contraction.
+    f32x16 acc2[4][1];
     const int ch0 = 64 * w + 4 * h;         // channel of xq[0][0].x
 
     auto timed_out = [&]() -> bool { return __hip_atomic_load((gu32*)p.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u; };
 
     // in-projection of the tile in xt (as [kMPad][32]) -> xq, through the (free) y tile region as [256][32]
     auto inproj_to_xq = [&]() {
-        inproj_tile(xt, p.head.winp, p.head.binp, p.head.nk_in, ytile, w, lane);
+        inproj_tile_nb(xt, p.head.winp, p.head.binp, p.head.nk_in, ytile, w, lane);
         __builtin_amdgcn_wave_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -394,6 +438,10 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
     publish_issue(0);
     for (int e = 0; e < p.n_evals; ++e) {
         const int t_e = p.eval_t[e];
+#pragma unroll
+        for (int ms = 0; ms < 2; ++ms)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc2[2 + ms][0][r] = 0.f;
         for (int l = 0; l < p.L; ++l, ++ph) {
             const bool last = (l == p.L - 1);
             const float* dsl = dsbuf + (ph & 1) * kC;
@@ -408,14 +456,25 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
             //     channels of frame j as 8 ds_write_b128 into the frame's row of the pair-ordered tile
             {
                 float* yrow = ytile + wn_row_of_frame(j, de);
+                if (own_cut) {
 #pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
+                    for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int c = ch0 + 32 * mb + 8 * q;
-                        const float4 d = *reinterpret_cast<const float4*>(dsl + c);
-                        *reinterpret_cast<float4*>(yrow + c) = fm_add_masked(xq[mb][q], d, in_t);
-                    }
+                        for (int q = 0; q < 4; ++q) {
+                            const int c = ch0 + 32 * mb + 8 * q;
+                            const float4 d = *reinterpret_cast<const float4*>(dsl + c);
+                            *reinterpret_cast<float4*>(yrow + c) = fm_add_masked(xq[mb][q], d, in_t);
+                        }
+                } else {
+#pragma unroll
+                    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const int c = ch0 + 32 * mb + 8 * q;
+                            const float4 d = *reinterpret_cast<const float4*>(dsl + c);
+                            *reinterpret_cast<float4*>(yrow + c) = fm_add(xq[mb][q], d);
+                        }
+                }
             }
             // (a) this tile's halo frames of phase ph (stored at the end of the previous phase / behind the head's input projection) are
             //     visible once every wave has drained; the barrier is the one the y tile needs anyway
@@ -470,13 +529,18 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
                 const float4 d = *reinterpret_cast<const float4*>(dsl + c);
 #pragma unroll
                 for (int side = 0; side < 2; ++side) {
-                    const bool have = side ? has_right : has_left;
+                    const bool have = side ? has_right : has_left, cut = side ? right_cut : left_cut;
+                    float* dst0 = side ? ytile + (16 + (tid >> 6)) * LDK + c : ytile + kWnOBase + (tid >> 6) * LDK + c;        // frame f = 4 g + tid / 64
+                    const int tf = (side ? t0 + 32 : t0 - kHalo) + (tid >> 6);
+                    if (!have) {
 #pragma unroll
-                    for (int g = 0; g < 2; ++g) {
-                        const int f = 4 * g + (tid >> 6);
-                        const int t = side ? t0 + 32 + f : t0 - kHalo + f;
-                        float* dst = side ? ytile + (16 + f) * LDK + c : ytile + kWnOBase + f * LDK + c;
-                        *reinterpret_cast<float4*>(dst) = fm_add_masked(hv[side][g], d, have && t < T);
+                        for (int g = 0; g < 2; ++g) *reinterpret_cast<float4*>(dst0 + 4 * g * LDK) = make_float4(0.f, 0.f, 0.f, 0.f);
+                    } else if (cut) {
+#pragma unroll
+                        for (int g = 0; g < 2; ++g) *reinterpret_cast<float4*>(dst0 + 4 * g * LDK) = fm_add_masked(hv[side][g], d, tf + 4 * g < T);
+                    } else {
+#pragma unroll
+                        for (int g = 0; g < 2; ++g) *reinterpret_cast<float4*>(dst0 + 4 * g * LDK) = fm_add(hv[side][g], d);
                     }
                 }
             }
@@ -522,6 +586,12 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
                 // output projection, all four row blocks (0,1 residual, 2,3 skip) in one pass
                 GemmPipe<4, 1, LDK, 256, 6, TileBT, 1, true> pipe2(p.w2p + ((size_t)l * 4 + w) * (32 * 256), lane, 32, bof2);
                 pipe2.start_a();
+                // the residual row blocks start from the bias of their channels (zeroed, they cost 32 moves here and 32 adds behind the
+                // contraction): b + sum of the products, requested in front of the gate
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) set4(acc2[mb][0], q, *reinterpret_cast<const float4*>(p.b2raw + (size_t)l * 2 * kC + ch0 + 32 * mb + 8 * q));
                 do_gate();
                 // the next layer's conditioner projection into the (dead) accumulators, under the out-projection.  (Issued HERE, in front of
                 // the barrier: beside the out-projection's MFMAs the 16 cold loads cost 2.5 k cycles of in-order waits, profiles/r5_07)
@@ -529,40 +599,20 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
                 dsbuf[((ph + 1u) & 1u) * kC + tid] = ds_next;       // visible behind the barrier (that half was last read in phase ph - 1)
                 __syncthreads();
                 LOOP_STAMP(4);
-                f32x16 acc2[4][1];
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc2[m][0][r] = 0.f;
-                float4 bq[2][4];            // residual-half bias of this lane's channels
                 pipe2.start_b();
-                pipe2.run(acc2, 0, 6);
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) bq[mb][q] = *reinterpret_cast<const float4*>(p.b2raw + (size_t)l * 2 * kC + ch0 + 32 * mb + 8 * q);
-                DSD_SB();
-                pipe2.run(acc2, 6, 32);
+                pipe2.template run_static<0, 32>(acc2);
                 LOOP_STAMP(5);
-                // residual in place: x' = (x + res + b) / sqrt(2) - the accumulators hold exactly the elements of xq
+                // residual in place: x' = (x + (b + res)) / sqrt(2) - the accumulators hold exactly the elements of xq
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const float4 v = get4(acc2[mb][0], q), x = xq[mb][q], bv = bq[mb][q];
+                        const float4 v = get4(acc2[mb][0], q), x = xq[mb][q];
                         constexpr float kInvSqrt2 = 1.0f / 1.41421354f;
-                        xq[mb][q] = make_float4((x.x + (v.x + bv.x)) * kInvSqrt2, (x.y + (v.y + bv.y)) * kInvSqrt2,
-                                                (x.z + (v.z + bv.z)) * kInvSqrt2, (x.w + (v.w + bv.w)) * kInvSqrt2);
+                        xq[mb][q] = make_float4((x.x + v.x) * kInvSqrt2, (x.y + v.y) * kInvSqrt2, (x.z + v.z) * kInvSqrt2, (x.w + v.w) * kInvSqrt2);
                     }
                 LOOP_STAMP(6);
-                publish_issue(ph + 1u);                             // the halo stores drain under the skip sum, the next prefetch and y tile
-#pragma unroll
-                for (int ms = 0; ms < 2; ++ms)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float4 a = get4(acc2[2 + ms][0], q), s = skp[ms][q];
-                        skp[ms][q] = (l == 0) ? a : make_float4(a.x + s.x, a.y + s.y, a.z + s.z, a.w + s.w);
-                    }
+                publish_issue(ph + 1u);                             // the halo stores drain under the next prefetch and y tile
                 LOOP_STAMP(7);
             } else {
                 // last layer: only the skip half (net.py:126 reads the skips; the residual is dead)
@@ -571,20 +621,8 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
                 do_gate();
                 dsbuf[((ph + 1u) & 1u) * kC + tid] = ds_next;       // visible behind the barrier
                 __syncthreads();
-                f32x16 acc2[2][1];
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc2[m][0][r] = 0.f;
                 pipe2.start_b();
-                pipe2.run(acc2, 0, 32);
-#pragma unroll
-                for (int ms = 0; ms < 2; ++ms)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float4 a = get4(acc2[ms][0], q), s = skp[ms][q];
-                        skp[ms][q] = (l == 0) ? a : make_float4(a.x + s.x, a.y + s.y, a.z + s.z, a.w + s.w);
-                    }
+                pipe2.template run_static<0, 32, 2>(acc2);           // onto row blocks 2, 3 of the set
             }
         }
 
@@ -603,7 +641,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
         for (int ms = 0; ms < 2; ++ms)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float4 s = skp[ms][q], bs = p.head.bskp[((w * 2 + ms) * 2 + h) * 4 + q];
+                const float4 s = get4(acc2[2 + ms][0], q), bs = p.head.bskp[((w * 2 + ms) * 2 + h) * 4 + q];
                 const float v[4] = {s.x + bs.x, s.y + bs.y, s.z + bs.z, s.w + bs.w};
 #pragma unroll
                 for (int ee = 0; ee < 4; ++ee)
@@ -618,7 +656,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
 #pragma unroll
                 for (int q = 0; q < 4; ++q) set4(acc[mb][0], q, p.head.bsp[((w * 2 + mb) * 2 + h) * 4 + q]);
             pipe_s.start_b();
-            pipe_s.run(acc, 0, 32);
+            pipe_s.template run_static<0, 32>(acc);
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -636,7 +674,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
 #pragma unroll
             for (int q = 0; q < 4; ++q) set4(acc[0][0], q, p.head.boutp[(w * 2 + h) * 4 + q]);
             pipe_o.start_b();
-            pipe_o.run(acc, 0, 32);
+            pipe_o.template run_static<0, 32>(acc);
             HEAD_STAMP(4);
             // (an opaque zero defined HERE keeps the 16 element indices - and the Philox products that hang on them - in this block: as loop
             // invariants of the evaluation loop they would live, spilled to scratch, across every contraction of the kernel)
@@ -706,7 +744,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_loop_wino(const LoopWinoParams 
         HEAD_STAMP(5);
         __syncthreads();
         HEAD_STAMP(6);
-        if (fuse) { inproj_to_xq(); publish_issue(ph); load_cp(0); }     // (layer 0's conditioner projection LAST: live across the in-projection, the 64 registers cost 35 spills in the sampler update)     // (layer 0's conditioner projection: under the input projection)
+        if (fuse) { inproj_to_xq(); publish_issue(ph); load_cp(0); }     // (layer 0's conditioner projection LAST: live across the in-projection, the 64 registers cost 35 spills in the sampler update)
         HEAD_STAMP(7);
     }
 #undef LOOP_STAMP

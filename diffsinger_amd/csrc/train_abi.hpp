@@ -24,7 +24,7 @@ static int tr_ncu() {
 }
 // The forward as ONE persistent launch per chunk of whole utterances (train_loop.hpp) instead of a launch per layer: on when an utterance fits
 // the co-resident grid (one workgroup per CU) and the chunks fill the chip at least as well as the per-layer grid does (the rule of
-// loop_applicable(), dsd.hip).  dsf_set_stack_mode: 1 automatic (default), 0 per-layer launches always (the A/B switch of tools/bench_train.py),
+// sampler_path(), dsd_path.hpp).  dsf_set_stack_mode: 1 automatic (default), 0 per-layer launches always (the A/B switch of tools/bench_train.py),
 // 2 persistent wherever an utterance fits the grid (tests of the chunked form on any shape).  A process-wide setting, read once per call:
 // the workspace layouts do not depend on it.  (The data-gradient chain of the backward pass had a persistent form too - k_trb_loop, round 2:
 // measured equal to the per-layer launches for 30 % more workspace, profiles/r03z - deleted in round 3.)

@@ -1,5 +1,5 @@
 // train_loop_wino.hpp - the forward of the fused training stack with the dilated convolution as WINOGRAD F(2,3) (gfx950; SURVEY.md section 8
-// row f3): k_tr_stack_fwd_w = the layer body of the inference loop k_loop_wino (dsd_loop_wino.hpp: pair-ordered frame-major y tile,
+// row f3): k_tr_stack_fwd_w = the layer body of the inference loop k_loop_wino_sa (dsd_loop_wino.hpp: pair-ordered frame-major y tile,
 // v_mfma_f32_16x16x4_f32 over 16 output pairs, transformed weights in consumption order with the per-period L2 touch, the conditioner
 // projection as the accumulators' initial values, publication merged into the next layer's top) behind the interface of k_tr_stack_fwd
 // (train_loop.hpp): one pass over the layers, no sampler head.
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_tr_stack_fwd_w(const TrLoopWino
         for (int q = 0; q < 4; ++q) skp[ms][q] = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
 
-    // the halo protocol of k_loop_wino: first / last 8 frames of x as write-through stores; drained, barrier and flag at the top of the NEXT layer
+    // the halo protocol of k_loop_wino_sa: first / last 8 frames of x as write-through stores; drained, barrier and flag at the top of the NEXT layer
     auto publish_issue = [&](unsigned phase) {
         float* hb = p.halo + ((size_t)(phase & 1) * p.ntiles_total + tile) * (2 * kC * 8);
         typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));

@@ -69,7 +69,7 @@ def test_evidence_refuses_a_summary_of_another_binary(tmp_path, monkeypatch):
     if not kernel_isa(cur):
         write_kernel_isa()
     isa = kernel_isa(cur)
-    name = 'k_loop_wino<1, 4>(LoopWinoParams)'
+    name = 'k_loop_wino_sa<1, 4>(LoopWinoParams)'         # the kernel behind the tag (the evidence files name it in kernel_isa_name)
     assert name in isa and len(isa) > 100
     monkeypatch.setattr(bench, 'ROOT', str(tmp_path))
     os.makedirs(tmp_path / 'profiles')

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(autouse=True)
 def _direct_convolution(monkeypatch):
-    monkeypatch.setenv('DSD_CONV', 'direct')         # read at dsd_create: every engine of this file runs k_loop, not k_loop_wino
+    monkeypatch.setenv('DSD_CONV', 'direct')         # read at dsd_create: every engine of this file runs k_loop, not k_loop_wino_sa
 
 
 def _run(name, loop_mode):
@@ -182,3 +182,68 @@ def test_starved_persistent_loop_is_loud_and_the_retry_succeeds():
     eng.set_loop_mode(1)                                        # re-armed: the persistent loop works again once the chip is free
     np.testing.assert_array_equal(run(check=True).cpu().numpy(), ref)
     assert eng.loop_mode() == 1 and eng.loop_timeouts() == 0
+
+
+def _plms_small():
+    """B = 2, T = 70 (three tiles per utterance, the last one cut), K = 12, interval 3: evaluations at t = 9 (RAW), 6 (HEUN), 6 (AB2), 3 (AB3),
+    0 (AB4) - every order of the PLMS schedule."""
+    import diffsinger_amd
+    from diffsinger_amd import hparams
+    from diffsinger_amd.synth import presets
+    pre = presets()['opencpop_ds60_rel']                       # dilation cycle 4: halos up to 8 frames
+    hparams.clear()
+    diffsinger_amd.use_preset('opencpop_ds60_rel')
+    torch.manual_seed(11)
+    net = diffsinger_amd.DIFF_DECODERS['wavenet'](hparams)
+    torch.nn.init.normal_(net.output_projection.weight, std=0.02)
+    B, T, K = 2, 70, 12
+    gd = diffsinger_amd.GaussianDiffusion(None, 80, net, timesteps=100, K_step=K, loss_type='l1', spec_min=pre['spec_min'],
+                                          spec_max=pre['spec_max']).cuda().eval()
+    g = torch.Generator(device='cuda').manual_seed(12)
+    cond = torch.randn(B, T, 256, device='cuda', generator=g).transpose(1, 2)
+    x_T = torch.randn(B, 1, 80, T, device='cuda', generator=g)
+    return gd, cond, x_T, int(hparams['residual_layers'])
+
+
+def test_plms_eager_equals_graph_equals_persistent_loop():
+    """ONE evaluation schedule (plan_evals, csrc/dsd.hip) feeds the captured graph, the eager launches and the persistent loop: per-layer
+    kernels through the cached graph, the same launches issued eagerly, and k_loop give the same bits."""
+    gd, cond, x_T, _ = _plms_small()
+    eng = gd._engine(cond)
+    outs = {}
+    for name, mode, graph in (('graph', 0, True), ('eager', 0, False), ('persistent', 1, True)):
+        eng.set_loop_mode(mode)
+        eng.set_use_graph(graph)
+        with torch.no_grad():
+            outs[name] = gd.inference(cond, x_T=x_T, K_step=12, pndm_speedup=3).cpu()
+        assert eng.loop_mode() == mode and eng.lat_split() == 0 and eng.conv_mode() == 0
+        assert eng.loop_timeouts() == 0
+    eng.set_use_graph(True)
+    assert torch.isfinite(outs['graph']).all()
+    assert torch.equal(outs['graph'], outs['eager'])
+    assert torch.equal(outs['graph'], outs['persistent'])
+
+
+def test_getters_report_the_decision_of_the_path_function():
+    """The handle-to-input glue of csrc/dsd.hip (path_of) against the pure function: the five getters of the prepared batch equal what
+    tests/path_table.cpp prints for this device's CU count under every loop mode and row-split request, both convolutions."""
+    from tests.test_path_decisions import decide
+    gd, cond, _, L = _plms_small()
+    eng = gd._engine(cond)
+    n_cu = torch.cuda.get_device_properties(cond.device).multi_processor_count
+    try:
+        for conv in (0, 1):
+            eng.set_conv_mode(conv)
+            for loop in (0, 1, 2, 3):
+                eng.set_loop_mode(loop)
+                for lat in (-1, 0, 2, 16):
+                    eng.set_lat_split(lat)
+                    want = decide(n_cu=n_cu, L=L, B=2, T=70, loop=loop, lat=lat, tile=0, conv=conv, split=0, graph=1, off=0)
+                    got = (eng.layer_tile(), eng.lat_split(), eng.conv_mode(), eng.loop_mode(), eng.loop_launches())
+                    exp = (want['frames'], want['G'], int(want['kind'] == 'persistent-winograd' or want['lat_wino'] == 1),
+                           int(want['kind'].startswith('persistent')), want['launches'])
+                    print(f'conv {conv} loop {loop} lat {lat}: (layer_tile, lat_split, conv_mode, loop_mode, loop_launches) = {got}, path function {exp}')
+                    assert got == exp, (conv, loop, lat, want)
+    finally:
+        eng.set_lat_split(-1)
+        eng.set_loop_mode(2)

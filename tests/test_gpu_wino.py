@@ -162,7 +162,7 @@ def test_results_do_not_depend_on_the_touch_lead_and_seeded_noise_matches_explic
 
 
 # (BASELINE configs[1] at full size - 8 x 1024, K = 100, rows against the oracle - runs on this loop in tests/test_gpu_fullsize.py::
-# test_config2_ddpm_k100_rows_vs_oracle_and_row_independence: the default path of that batch IS k_loop_wino; 5.0e-6 / 6.0e-6 in profiles/r5_01_pytest_wino.txt)
+# test_config2_ddpm_k100_rows_vs_oracle_and_row_independence: the default path of that batch IS k_loop_wino_sa; 5.0e-6 / 6.0e-6 in profiles/r5_01_pytest_wino.txt)
 
 
 def test_starved_winograd_loop_is_loud_and_the_retry_succeeds():

@@ -16,7 +16,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from diffsinger_amd.build import FLAGS as _LIB_FLAGS  # noqa: E402
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'kernel_isa_hashes.json')
-GOLDEN_WINO_SA = os.path.join(ROOT, 'tests', 'golden', 'kernel_isa_hashes_wino_sa.json')   # k_loop_wino_sa (tests/test_wino_acc_copies.py): --update refreshes its entries
 FLAGS = [f for f in _LIB_FLAGS if f != '-shared'] + ['--cuda-device-only', '-S']       # the library's own flags, device-only assembly
 
 
@@ -75,8 +74,5 @@ if __name__ == '__main__':
         json.dump({'note': 'sha1 of the normalised gfx950 assembly of every kernel that has run (and passed its parity tests) on the MI355X; '
                            'tools/isa_hashes.py --update after a GPU run', 'kernels': {k: h[k] for k in keep}}, open(GOLDEN, 'w'), indent=1)
         print(f'{len(keep)} kernels written to {GOLDEN} ({len(h) - len(keep)} not-yet-run kernels left out)')
-        side = json.load(open(GOLDEN_WINO_SA))
-        side['kernels'] = {k: h[k] for k in side['kernels']}
-        json.dump(side, open(GOLDEN_WINO_SA, 'w'), indent=1)
     else:
         print(json.dumps(h, indent=1))

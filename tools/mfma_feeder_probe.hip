@@ -1,10 +1,10 @@
 // Developer probe (GPU), round 6: WHO should fetch the A stream of an fp32 MFMA loop, and into what?
 // tools/mfma_filler_probe.hip priced a 1 KiB `buffer_load_dwordx4` issued by the computing wave itself at ~10-16 cycles of matrix time (8 % of
-// k_loop_wino's contraction: 4 loads per 16 short MFMAs) while a `ds_read_b128` costs under one cycle.  This probe asks whether that price is
+// k_loop_wino_sa's contraction: 4 loads per 16 short MFMAs) while a `ds_read_b128` costs under one cycle.  This probe asks whether that price is
 // attached to the ISSUING wave (then a second, loader wave per SIMD could pay it instead) or to the CU (then nothing helps), and whether the
 // gfx950 LDS-DMA form (`buffer_load_dwordx4 ... lds`: no destination registers) is any cheaper:
 //   mode 0  4 computing waves (one per SIMD), v_mfma_f32_16x16x4_f32 stream, nothing else
-//   mode 1  the same waves issue 4 x buffer_load_dwordx4 -> registers per 16 MFMAs (what k_loop_wino does)
+//   mode 1  the same waves issue 4 x buffer_load_dwordx4 -> registers per 16 MFMAs (what k_loop_wino_sa does)
 //   mode 2  the same waves issue 4 x buffer_load_dwordx4 ... lds per 16 MFMAs and read the data back with 4 x ds_read_b128
 //   mode 3  8 waves: the computing waves only read LDS (4 x ds_read_b128 per 16 MFMAs); a LOADER wave per SIMD issues the 4 loads -> registers
 //   mode 4  8 waves: as 3, the loader waves use the LDS-DMA form
@@ -17,7 +17,7 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 
-constexpr unsigned kStream = 2u << 20;      // bytes walked by the loads (k_loop_wino: 2 MiB per layer, the same addresses in every workgroup)
+constexpr unsigned kStream = 2u << 20;      // bytes walked by the loads (k_loop_wino_sa: 2 MiB per layer, the same addresses in every workgroup)
 
 template <int MODE, int SLEEP>
 __global__ __launch_bounds__(MODE >= 3 ? 512 : 256, 1) void probe(const float4* __restrict__ w, float* out, unsigned long long* cyc, int rounds) {

@@ -107,7 +107,7 @@ def provenance(kern, tag=None, observed=()):
     out = {'build_id': binary_id()}
     hits = {n: h for n, h in kernel_isa().items() if kern in n}
     if len(hits) > 1 and tag:
-        # 'k_loop_wino' names two instantiations; the kernel_tag of the summary ('k_loop_wino<1, 4>', possibly followed by a note in
+        # a kernel name like 'k_loop_wino_sa' names two instantiations; the kernel_tag of the summary ('k_loop_wino<1, 4>', possibly followed by a note in
         # parentheses) names the one that ran - r6_16's loop_pmc.json went unstamped without this and the next rebuild orphaned it
         t = tag.split(' (')[0]
         hits = {n: h for n, h in hits.items() if n.startswith(t)}

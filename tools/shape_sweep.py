@@ -19,7 +19,7 @@ from diffsinger_amd import hparams
 from diffsinger_amd.synth import presets
 
 F_EXEC = 21_053_440            # direct convolution (per-layer / latency kernels, k_loop)
-F_EXEC_WINO = 15_810_560       # Winograd F(2,3) convolution (k_loop_wino, the default of the persistent path)
+F_EXEC_WINO = 15_810_560       # Winograd F(2,3) convolution (k_loop_wino_sa, the default of the persistent path)
 PEAK_TF = 157.3
 SHAPES = [(1, 512), (1, 1550), (4, 777), (8, 1000), (8, 1024), (5, 1550), (3, 5000), (2, 8000), (16, 2048)]
 

@@ -1,5 +1,5 @@
 """Developer tool (GPU): A/B of the persistent loop's convolution forms on BASELINE configs[1] (8 x 1024, K = 100 DDPM): the direct K = 768 form
-(k_loop) against the Winograd F(2,3) form (k_loop_wino) over the lead of the L2 touch of its weight stream.  One JSON line
+(k_loop) against the Winograd F(2,3) form (k_loop_wino_sa) over the lead of the L2 touch of its weight stream.  One JSON line
 per variant: ms per sampling call (HIP events, 3 calls), mel-frames/s of the loop alone, executed TFLOP/s and the fraction of the fp32 MFMA
 peak, max-abs difference of the normalised x against the direct form."""
 import json, os, sys
