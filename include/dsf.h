@@ -48,7 +48,9 @@ int dsf_layer_norm(const float* in, const float* gamma, const float* beta, float
 
 /* The attention core of F.multi_head_attention_forward as MultiheadAttention.forward calls it (common_layers.py:243-263):
  * per head softmax((q * head_dim**-0.5) k^T + key_padding_mask) v.  qkv [B][3C][TS] (q | k | v rows, head h = rows
- * [h*128, h*128+128) of each), key_pad [B][T] bytes (nonzero = padded key) or NULL, out [B][C][TS].  head_dim 128. */
+ * [h*128, h*128+128) of each), key_pad [B][T] bytes (nonzero = padded key) or NULL, out [B][C][TS].  head_dim 128.
+ * An utterance whose keys are ALL padded gets an output of exactly 0 (the torch expression gives NaN there); the other utterances of the
+ * batch carry the bits they carry without it. */
 int dsf_attention(const float* qkv, const uint8_t* key_pad, float* out, int32_t B, int32_t C, int32_t heads, int32_t T, void* stream);
 
 /* BACKWARD of the two operators above - what torch autograd runs for nn.LayerNorm and F.multi_head_attention_forward when FastSpeech2 is trained
