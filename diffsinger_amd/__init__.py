@@ -13,6 +13,9 @@ Public surface mirrors the reference's own plugin API for this path:
     ParallelWaveGANDiscriminator        modules/parallel_wavegan/models/parallel_wavegan.py:207, forward and backward on HIP (+ pwg_disc_op,
                                         lsgan_loss_op, generator_loss, discriminator_loss: modules/hifigan/hifigan.py:337-365;
                                         diffsinger_amd/pwg_disc.py)
+    pwg_generator_losses, pwg_discriminator_losses, pwg_training_step
+                                        the ParallelWaveGAN trainer's two objectives and one step of it (configs/tts/pwg.yaml) on
+                                        ParallelWaveGANGenerator.forward_train (diffsinger_amd/pwg_train.py, + pwg_gen_op)
     pe_losses(output, sample, hp), pe_training_step(model, sample, hp)
                                         PitchExtractionTask.run_model / ._training_step (tasks/tts/pe.py:111-155) on the HIP PitchExtractor
                                         (diffsinger_amd/pe.py)
@@ -24,6 +27,7 @@ from .hparams import hparams, use_preset  # noqa: F401
 __all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiffusion', 'register', 'hparams', 'use_preset',
            'STFTLoss', 'MultiResolutionSTFTLoss', 'stft_adjoint_op', 'spectral_loss_op',
            'ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss',
+           'pwg_gen_op', 'pwg_generator_losses', 'pwg_discriminator_losses', 'pwg_training_step',
            'pe_losses', 'pe_training_step']
 
 
@@ -43,6 +47,9 @@ def __getattr__(name):      # lazy: torch-heavy modules load on first use
     if name in ('ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss'):
         from . import pwg_disc
         return getattr(pwg_disc, name)
+    if name in ('pwg_gen_op', 'pwg_generator_losses', 'pwg_discriminator_losses', 'pwg_training_step'):
+        from . import pwg_train
+        return getattr(pwg_train, name)
     if name in ('pe_losses', 'pe_training_step'):
         from . import pe
         return getattr(pe, name)

@@ -43,7 +43,10 @@ SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'ds
                'dsv_spectral_loss_backward',
                'dsv_pwgd_tile', 'dsv_pwgd_wgrad_split', 'dsv_pwgd_wgrad_workspace_floats', 'dsv_pwgd_edge_workspace_floats', 'dsv_pwgd_layer', 'dsv_pwgd_wgrad',
                'dsv_pwgd_first', 'dsv_pwgd_first_backward', 'dsv_pwgd_last', 'dsv_pwgd_last_backward', 'dsv_pwgd_lsgan_workspace_floats', 'dsv_pwgd_lsgan',
-               'dsv_pwgd_lsgan_backward']
+               'dsv_pwgd_lsgan_backward',
+               'dsv_pwgt_wgrad_split', 'dsv_pwgt_wgrad_workspace_floats', 'dsv_pwgt_upsample_workspace_floats', 'dsv_pwgt_layer', 'dsv_pwgt_gate_backward',
+               'dsv_pwgt_conv_backward', 'dsv_pwgt_wgrad_conv', 'dsv_pwgt_wgrad_out', 'dsv_pwgt_wgrad_relu', 'dsv_pwgt_rowdot', 'dsv_pwgt_last_dgrad',
+               'dsv_pwgt_relu_mask', 'dsv_pwgt_upsample_backward', 'dsv_pwgt_convin_wgrad']
 
 _fp = C.POINTER(C.c_float)
 _fpp = C.POINTER(C.c_void_p)
@@ -262,6 +265,23 @@ def load():
     lib.dsv_pwgd_lsgan_workspace_floats.restype = i64
     lib.dsv_pwgd_lsgan.argtypes = [vp, f32, vp, vp, i64, vp]
     lib.dsv_pwgd_lsgan_backward.argtypes = [vp, f32, vp, vp, i64, vp]
+    lib.dsv_pwgt_wgrad_split.argtypes = []
+    lib.dsv_pwgt_wgrad_split.restype = i32
+    lib.dsv_pwgt_wgrad_workspace_floats.argtypes = [i32, i32, i32]
+    lib.dsv_pwgt_wgrad_workspace_floats.restype = i64
+    lib.dsv_pwgt_upsample_workspace_floats.argtypes = [i64, i32]
+    lib.dsv_pwgt_upsample_workspace_floats.restype = i64
+    lib.dsv_pwgt_layer.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.dsv_pwgt_gate_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+    lib.dsv_pwgt_conv_backward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.dsv_pwgt_wgrad_conv.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.dsv_pwgt_wgrad_out.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+    lib.dsv_pwgt_wgrad_relu.argtypes = [vp, vp, vp, vp, i32, i32, vp]
+    lib.dsv_pwgt_rowdot.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.dsv_pwgt_last_dgrad.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.dsv_pwgt_relu_mask.argtypes = [vp, vp, vp, f32, i64, i32, vp]
+    lib.dsv_pwgt_upsample_backward.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]
+    lib.dsv_pwgt_convin_wgrad.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('dsd_abi_version',):

@@ -8,6 +8,9 @@ ConvInUpsampleNetwork (layers/upsample.py:130-183) -> ReLU / 1x1 / ReLU / 1x1.  
 index plumbing (embedding lookup, padding, cropping).  This build covers the configuration the reference ships and trains: kernel_size 3,
 residual / gate / skip channels 64 / 128 / 64, non-causal, `ConvInUpsampleNetwork`; anything else raises.
 
+`forward_train` is the differentiable form of the same forward for the ParallelWaveGAN trainer (pwg_train.py, csrc/pwg_train.hpp): bit-identical
+values, gradients for every parameter; `forward` itself stays inference-only.
+
 `PWG` mirrors vocoders/pwg.py:54-117 (`spec2wav`)."""
 from __future__ import annotations
 
@@ -122,6 +125,7 @@ class ParallelWaveGANGenerator(nn.Module):
         assert layers % stacks == 0
         self.in_channels, self.out_channels, self.aux_channels = in_channels, out_channels, aux_channels
         self.layers, self.stacks, self.kernel_size = layers, stacks, kernel_size
+        self.dropout = float(dropout)
         self.upsample_scales = [int(s) for s in upsample_params['upsample_scales']]
         wn = bool(use_weight_norm)
         self.first_conv = _WN((residual_channels, in_channels, 1), True, wn)
@@ -230,6 +234,43 @@ class ParallelWaveGANGenerator(nn.Module):
         wp, b = self._packed('last3', [l3], lambda: (l3.plain_weight(), l3.bias.detach()))
         o = ops.conv(o, T, wp, b, 1, 64, 1, 0, 1, pre_slope=0.0)
         return o[:, :, :T]
+
+
+    # -- training ------------------------------------------------------------------------------------------------------------
+    def _train_params(self):
+        """plain weights (the weight-norm expression g * v / ||v|| as a torch expression, like pwg_disc.py) and biases in PwgGenFunction's order"""
+        def w(m):
+            return torch._weight_norm(m.weight_v, m.weight_g, 0) if hasattr(m, 'weight_g') else m.weight
+        up = self.upsample_net
+        ps = [w(self.first_conv), self.first_conv.bias, w(up.conv_in)]
+        ps += [w(up.upsample.up_layers[2 * i + 1]) for i in range(len(self.upsample_scales))]
+        for blk in self.conv_layers:
+            ps += [w(blk.conv), blk.conv.bias, w(blk.conv1x1_aux), w(blk.conv1x1_out), blk.conv1x1_out.bias, w(blk.conv1x1_skip), blk.conv1x1_skip.bias]
+        l1, l3 = self.last_conv_layers[1], self.last_conv_layers[3]
+        return ps + [w(l1), l1.bias, w(l3), l3.bias]
+
+    def forward_train(self, x, c, return_saved=False):
+        """The differentiable forward: x [B,1,T] noise, c [B,aux,T / hop + 2 * context window] padded mel -> [B,1,T] float32, bit-identical to
+        forward() on the same parameters, through ONE autograd node (pwg_train.PwgGenFunction) that returns the gradient of every parameter,
+        weight-normed or plain.  As in the reference's autograd the last block's conv1x1_out gets no gradient (None): that block's residual
+        output is never read.  x and c get no gradient.  return_saved=True: (y, [S, o1]), the inputs of the two ReLUs of last_conv_layers as
+        [B,64,T] views without gradient (pwg_train.pwg_gen_op)."""
+        if self.use_pitch_embed:
+            raise NotImplementedError('forward_train with use_pitch_embed=True: the embedding and c_proj need the conditioning gradient through conv_in')
+        if self.dropout != 0.0:
+            raise NotImplementedError(f'forward_train with dropout={self.dropout}: the training kernels have no dropout (configs/tts/pwg.yaml: 0.0)')
+        if c is None:
+            raise NotImplementedError('ParallelWaveGANGenerator without local conditioning')
+        if x.requires_grad or c.requires_grad:
+            raise NotImplementedError('forward_train: no gradient with respect to the noise x or the conditioning c (detach them)')
+        if x.dim() != 3 or x.shape[1] != 1 or c.dim() != 3 or c.shape[0] != x.shape[0] or c.shape[1] != self.aux_channels:
+            raise ValueError(f'forward_train: x must be [B,1,T] and c [B,{self.aux_channels},T\'], got {tuple(x.shape)} and {tuple(c.shape)}')
+        if x.device.type != 'cuda' or c.device != x.device:
+            raise RuntimeError('ParallelWaveGANGenerator: the HIP path needs device tensors (there is no CPU path in this package)')
+        from .pwg_train import pwg_gen_op
+        meta = dict(aux=self.aux_channels, k_in=2 * self.upsample_net.aux_context_window + 1, scales=list(self.upsample_scales),
+                    dilations=[blk.dilation for blk in self.conv_layers])
+        return pwg_gen_op(x, c, meta, self._train_params(), return_saved=return_saved)
 
 
 def load_pwg_model(config_path, checkpoint_path, stats_path=None, device=None):

@@ -312,6 +312,63 @@ int64_t dsv_pwgd_lsgan_workspace_floats(int64_t n);
 int dsv_pwgd_lsgan(const float* d, float target, float* workspace, float* out, int64_t n, void* stream);
 int dsv_pwgd_lsgan_backward(const float* d, float target, const float* grad_out, float* G, int64_t n, void* stream);
 
+/* PWG generator training: the training forward of a gated residual block and the backward of every piece of ParallelWaveGANGenerator
+ * (modules/parallel_wavegan/models/parallel_wavegan.py:21-177, layers/residual_block.py:96-129, layers/upsample.py:63-183) - csrc/pwg_train.hpp.
+ * Activations [B][C][LS(L)] channel-major; every call leaves [L, LS) of its outputs at zero.  fp32 MFMA contractions, no atomics, fixed
+ * summation order (two calls are bitwise equal); nothing allocates or synchronises.  B in [1, 65535], L in [1, 2^30], n_aux a multiple of 8 in
+ * [0, 128], dil >= 1; anything else is refused with DSD_ERR_INVALID before any launch.  s = sqrt(0.5).
+ *
+ * dsv_pwgt_layer: dsv_pwg_layer (same arguments, bitwise the same x_out and skip) that also stores the gate pre-activations
+ *   a_out [B][128][LS] = W_conv * [x(t - d); x(t); x(t + d)] + b_conv + W_aux c (rows 0..63 the tanh half, 64..127 the sigmoid half).
+ * dsv_pwgt_gate_backward: dz = W_skip^T d_skip + W_out^T (s dx_next), da[0:64] = dz sigmoid(g) (1 - tanh(a)^2), da[64:128] = dz tanh(a) sigmoid(g)
+ *   (1 - sigmoid(g)) with tanh / sigmoid recomputed from `a` by the forward's formulas.  w2t_packed = dsv_pack_weight of [64][128][1]: row ci,
+ *   columns 0..63 = W_skip[co][ci], 64..127 = W_out[co][ci].  dx_next NULL (the last block: its residual output is never read): the out half
+ *   is not multiplied.  Several blocks' matrices may be packed by ONE dsv_pack_weight call of [n * 64][128][1]: block i's stream starts
+ *   2 * i * 16 * 256 floats into the buffer.
+ * dsv_pwgt_conv_backward: dx = s dx_next + sum_tap W_conv[:, :, tap]^T da(t - (tap - 1) dil) (zero outside [0, L)); dx_next may be NULL;
+ *   w1t_packed = dsv_pack_weight of [64][384][1]: row ci, column tap * 128 + co = W_conv[co][ci][tap] (block i at 2 * i * 48 * 256 floats).
+ *   n_aux > 0: dc [B][n_aux][LS] (+)= W_aux^T da - written when first != 0, added to otherwise; wauxt_packed = dsv_pack_weight of
+ *   [R][128][1], R = n_aux rounded up to 32: row r, column co = W_aux[co][r], rows >= n_aux zero (block i at (R / 32) * i * 16 * 256 floats).
+ *   dx must not alias dx_next.
+ * dsv_pwgt_wgrad_*: gradients of the 128-row matrices, out = dW [128][N] followed by db [128]; split partials on the MFMA into `workspace`
+ *   (dsv_pwgt_wgrad_workspace_floats(B, L, N) = B * ceil(L / dsv_pwgt_wgrad_split()) * (128 N + 128) floats; -1: bad shape), then the splits added
+ *   in index order in float64.
+ *     _conv: N = 192 + n_aux, dW = sum_t da(t) [x(t - dil); x(t); x(t + dil); c(t)]^T (columns tap * 64 + ci, then the aux channels; the columns
+ *            of a tap that lies outside the signal for every t are exact zeros), db = sum_t da.
+ *     _out:  N = 64, rows 0..63 = sum_t s dx_next(t) z(t)^T (zeros when dx_next is NULL), rows 64..127 = sum_t d_skip(t) z(t)^T, z = tanh(a[0:64])
+ *            sigmoid(a[64:128]) recomputed from `a`; db alike.
+ *     _relu: N = 64, rows 0..63 = sum_t g(t) relu(saved(t))^T with g, saved [B][64][LS] (last_conv_layers[1]); rows 64..127 zero.
+ * dsv_pwgt_rowdot: out[2 c] = sum_b sum_t P q(Q), out[2 c + 1] = sum_b sum_t P for c < C; P is [B][C][LS] when p_per_channel else [B][LS]
+ *   shared by every channel, Q alike; q = relu when relu_q.  float64 sums in a fixed order.  (first_conv: P = dx0, Q = the noise;
+ *   last_conv_layers[3]: P = the output gradient, Q = its saved input.)
+ * dsv_pwgt_last_dgrad: out[b][c][t] = w[c] g[b][t] where saved[b][c][t] > 0, else 0 (g [B][LS], saved / out [B][C][LS]).
+ * dsv_pwgt_relu_mask: out = scale * g where saved > 0, else 0, on `rows` rows of LS(L) samples.
+ * dsv_pwgt_upsample_backward: one stage of dsv_pwg_upsample.  g [rows][LS(L_in * scale)], in [rows][LS(L_in)], filter [2 scale + 1] ->
+ *   dw [2 scale + 1] (float64 partials per row in `workspace`, dsv_pwgt_upsample_workspace_floats(rows, scale) floats, 8-byte aligned, added in
+ *   row order) and, when din is not NULL, din [rows][LS(L_in)].
+ * dsv_pwgt_convin_wgrad: dw[co][ci][k] = sum_b sum_t g[b][co][t] c[b][ci][t + k], g [B][C][LS(L_out)], c [B][C][LS(L_out + K - 1)] (conv_in: no
+ *   padding); float64, fixed order. */
+int32_t dsv_pwgt_wgrad_split(void);
+int64_t dsv_pwgt_wgrad_workspace_floats(int32_t B, int32_t L, int32_t n_cols);
+int64_t dsv_pwgt_upsample_workspace_floats(int64_t rows, int32_t scale);
+int dsv_pwgt_layer(const float* x, const float* c, const float* w1_packed, const float* b1, const float* w2_packed, const float* b2, float* x_out,
+                   float* skip, float* a_out, int32_t B, int32_t L, int32_t n_aux, int32_t dil, int32_t first, void* stream);
+int dsv_pwgt_gate_backward(const float* dx_next, const float* d_skip, const float* a, const float* w2t_packed, float* da, int32_t B, int32_t L,
+                           void* stream);
+int dsv_pwgt_conv_backward(const float* da, const float* dx_next, const float* w1t_packed, const float* wauxt_packed, float* dx, float* dc, int32_t B,
+                           int32_t L, int32_t n_aux, int32_t dil, int32_t first, void* stream);
+int dsv_pwgt_wgrad_conv(const float* da, const float* x, const float* c, float* workspace, float* out, int32_t B, int32_t L, int32_t n_aux,
+                        int32_t dil, void* stream);
+int dsv_pwgt_wgrad_out(const float* dx_next, const float* d_skip, const float* a, float* workspace, float* out, int32_t B, int32_t L, void* stream);
+int dsv_pwgt_wgrad_relu(const float* g, const float* saved, float* workspace, float* out, int32_t B, int32_t L, void* stream);
+int dsv_pwgt_rowdot(const float* P, const float* Q, float* out, int32_t B, int32_t C, int32_t L, int32_t p_per_channel, int32_t q_per_channel,
+                    int32_t relu_q, void* stream);
+int dsv_pwgt_last_dgrad(const float* g, const float* saved, const float* w, float* out, int32_t B, int32_t C, int32_t L, void* stream);
+int dsv_pwgt_relu_mask(const float* g, const float* saved, float* out, float scale, int64_t rows, int32_t L, void* stream);
+int dsv_pwgt_upsample_backward(const float* g, const float* in, const float* filter, float* workspace, float* din, float* dw, int64_t rows,
+                               int32_t L_in, int32_t scale, void* stream);
+int dsv_pwgt_convin_wgrad(const float* g, const float* c, float* dw, int32_t B, int32_t C, int32_t K, int32_t L_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
