@@ -336,7 +336,7 @@ extern "C" int dsd_get_layer_tile(dsd_handle* h) { return h ? path_of(h).layer_f
 
 // Function attributes (dynamic LDS above 64 KiB) belong to a DEVICE's code object: true the first time call site `site` is reached on the
 // current device - a process that drives several GPUs (the reference's DP threads, utils/pl_utils.py:146-154) sets them on each.
-// site ids in use (one per call site, never shared): 1, 2 dsd.hip; 10, 11 fs2_abi.hpp; 30 train_abi.hpp; 40 voc_abi.hpp (ParallelWaveGAN); 41 pwg_train_abi.hpp; 700 - 702 voc_stft_abi.hpp; 703 voc_stft_loss_abi.hpp
+// site ids in use (one per call site, never shared): 1, 2 dsd.hip; 10, 11 fs2_abi.hpp; 30 train_abi.hpp; 40 voc_abi.hpp (ParallelWaveGAN); 41 pwg_train_abi.hpp; 700 - 702 voc_stft_abi.hpp; 703 voc_stft_loss_abi.hpp; 8xx / 18xx hifigan_train_abi.hpp
 static bool first_on_device(int site) {
     static std::mutex mu;
     static std::set<std::pair<int, int>> seen;
@@ -1445,4 +1445,5 @@ extern "C" int dsd_debug_layer_timeline(dsd_handle* h, int32_t layer, int32_t t,
 #include "voc_stft_loss_abi.hpp"
 #include "pwg_disc_abi.hpp"
 #include "pwg_train_abi.hpp"
+#include "hifigan_train_abi.hpp"
 #include "pe_train.hpp"

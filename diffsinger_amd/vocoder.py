@@ -12,8 +12,9 @@ What runs where: every Conv1d / ConvTranspose1d with the leaky_relu in front of 
 `/ num_kernels` / source add / tanh behind it is ONE launch of k_voc_conv (fp32 MFMA); the sine source (two cumulative
 sums over the sample axis, sin, uv / noise mix, Linear + tanh) and the strided noise convolutions are their own kernels.
 torch is used for buffers, the one-time weight preparation (weight-norm fold, polyphase form of the transposed
-convolutions) and the random draws of the source module.  Inference only; no CPU path: forward raises when the tensors
-are not on the MI355X."""
+convolutions) and the random draws of the source module.  No CPU path: forward raises when the tensors are not on the
+MI355X.  `forward()` is the inference path (no_grad, fused chains, cached packed weights); `forward_train()` is the same
+forward through one autograd node with a HIP backward (hifigan_train.py, csrc/hifigan_train.hpp)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -650,6 +651,47 @@ class HifiGanGenerator(nn.Module):
             x = self._stage_resblocks(i, x, L)
         x = self._conv('post', self.conv_post, x, L, pre_slope=0.01, act=1)                                  # F.leaky_relu default slope, tanh
         return x[:, :, :L].contiguous()
+
+    # ---- training --------------------------------------------------------------------------------------------------------------
+    def _train_params(self):
+        """(plain weight, bias) per parameter holder in hifigan_train.param_layout's order; the weight-norm expression g * v / ||v|| is a torch
+        expression (like pwg.py): autograd carries the plain weight's gradient on to weight_g and weight_v"""
+        from .hifigan_train import param_layout
+        ps = []
+        for prefix, _ in param_layout(self.h):
+            m = self.get_submodule(prefix[:-1])
+            ps += [torch._weight_norm(m.weight_v, m.weight_g, 0) if hasattr(m, 'weight_g') else m.weight, m.bias]
+        return ps
+
+    def forward_train(self, x, f0=None, *, rand_ini: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, return_saved=False):
+        """The differentiable forward: the arguments of forward(), the output bitwise equal to forward() on the same inputs and source draws,
+        through ONE autograd node (hifigan_train.HifiGanGenFunction) that returns the gradient of every parameter, weight-normed or plain.
+        x, f0 and the source draws get no gradient.  return_saved=True: (y, pre, sine_waves) - the inputs of the device's leaky ReLUs in call
+        order as unpadded [B,C,L] views, and for NSF the mixed sines [B,L,9] the source's Linear multiplied (no gradient flows through them)."""
+        if self.c_out != 1:
+            raise NotImplementedError('forward_train with c_out != 1')
+        for name, t in (('x', x), ('f0', f0), ('rand_ini', rand_ini), ('noise', noise)):
+            if t is not None and t.requires_grad:
+                raise NotImplementedError(f'forward_train: no gradient with respect to {name} (detach it)')
+        if x.device.type != 'cuda':
+            raise RuntimeError('HifiGanGenerator: the HIP vocoder has no CPU path - move the module and its inputs to the MI355X')
+        if x.dim() != 3 or x.shape[1] != 80:
+            raise ValueError(f'forward_train: x must be [B,80,T], got {tuple(x.shape)}')
+        B, _, T = x.shape
+        if f0 is not None:
+            if not self.use_pitch_embed:
+                raise ValueError('f0 given but the generator was built without use_pitch_embed')
+            hop = int(np.prod(self.h['upsample_rates']))
+            if hop & (hop - 1):
+                raise NotImplementedError('nearest f0 upsampling is index // hop here: exact for power-of-two hop sizes only')
+            H = self.harmonic_num + 1
+            if rand_ini is None:                                     # the draws of forward(), in the reference's order
+                rand_ini = torch.rand(B, H, device=x.device)
+            if noise is None:
+                noise = torch.randn(B, T * hop, H, device=x.device)
+                torch.randn(B, T * hop, 1, device=x.device)
+        from .hifigan_train import hifigan_gen_op
+        return hifigan_gen_op(x, f0, rand_ini, noise, self.h, self._train_params(), return_saved=return_saved)
 
 
 VOCODERS = {}

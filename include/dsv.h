@@ -369,6 +369,55 @@ int dsv_pwgt_upsample_backward(const float* g, const float* in, const float* fil
                                int32_t L_in, int32_t scale, void* stream);
 int dsv_pwgt_convin_wgrad(const float* g, const float* c, float* dw, int32_t B, int32_t C, int32_t K, int32_t L_out, void* stream);
 
+/* HiFi-GAN generator training: the backward of every piece of HifiGanGenerator.forward (modules/hifigan/hifigan.py:30-92, :104-169,
+ * modules/parallel_wavegan/models/source.py:518-531) - csrc/hifigan_train.hpp.  The training forward is the one-launch-per-convolution path above
+ * (dsv_conv1d / dsv_conv1d_folded): every convolution's input is a tensor in memory, and the leaky ReLU in front of it is applied while staging.
+ * Activations [B][C][LS(L)] channel-major; every call leaves [L, LS) of its outputs at zero.  No atomics, fixed summation order (two calls are
+ * bitwise equal); nothing allocates or synchronises; everything is enqueued on `stream`.  B in [1, 65535], L (times `up`) in [1, 2^30], channels
+ * in [1, 1024], taps within +-48 samples; anything else is refused with DSD_ERR_INVALID before any launch.  m(x) = x > 0 ? 1 : slope.
+ *
+ * dsv_hgt_act_floats(B, C, L) = B * C * LS(L): the length of an activation; dsv_hgt_wgrad_workspace_floats(B, L, Co, Ci, K, up) =
+ *   B * ceil(L / dsv_hgt_wgrad_split()) * (Co * up) * (Ci * K): the workspace of dsv_hgt_conv_wgrad (-1: bad shape).
+ * dsv_hgt_conv_dgrad: dx[b][i][t] = (m(x_saved) * sum_o sum_k w[o][i][k] g[b][o][t - k dil + pad] + residual + sum_in) / divide, g [B][Cg][LS],
+ *   x_saved / residual / sum_in / dx [B][C][LS] (x_saved NULL: m = 1; residual / sum_in NULL: absent).  wt_packed = dsv_pack_weight of the flipped,
+ *   transposed filter W'[i][o][k'] = w[o][i][K - 1 - k'] as [C][Cg][K]; `pad` is the FORWARD convolution's padding.  fp32 MFMA.
+ * dsv_hgt_conv_wgrad: dw[row][k][ci] = sum_b sum_t g[b][row / up][t up + row % up] lrelu(x[b][ci][t + k dil - pad], slope), row < Co * up,
+ *   x [B][Ci][LS(L)], g [B][Co][LS(L up)] - note the layout [rows][K][Ci].  up = 1: a convolution's weight gradient.  up = u: the weight gradient
+ *   of a transposed convolution in its polyphase form (rows co * u + phase at the input rate, K and pad of that form).  Split partials on the
+ *   fp32 MFMA into `workspace` (its length in floats is passed; shorter than dsv_hgt_wgrad_workspace_floats: refused), then the splits added in
+ *   index order in float64, rounded once.
+ * dsv_hgt_bias_grad: db[c] = sum_b sum_t g[b][c][t], float64 in a fixed order: partial sums per (channel, batch row, chunk of 1024 samples) into
+ *   `workspace` (dsv_hgt_bias_workspace_floats(B, C, L) = 2 C B ceil(L / 1024) floats, 8-byte aligned, its length passed; shorter: refused), then
+ *   one reduce per channel.
+ * dsv_hgt_upsample_dgrad: ConvTranspose1d(Ci -> Co, kernel K, stride up, padding (K - up) / 2) behind a leaky ReLU, data gradient:
+ *   dx[b][ci][q] = m(x_saved) sum_co sum_j w[ci][co][j] g[b][co][q up + j - pad] / divide; w is the plain weight [Ci][Co][K].
+ * dsv_hgt_tanh_backward: out[b][t] = gy[b][t] (1 - y[b][t]^2); gy [B][L] contiguous, y / out [B][LS].
+ * dsv_hgt_noise_conv_backward: dsv_noise_conv's backward from g [B][C][LS(L_out)]: dw [C][K], db [C] (float64 sums in a fixed order; db through
+ *   `workspace` of dsv_hgt_bias_workspace_floats(B, C, L_out) floats like dsv_hgt_bias_grad) and dhar [B][LS(L_har)] - written when first != 0,
+ *   added to otherwise (the stages accumulate in call order).
+ * dsv_hgt_source_mix: sines [B][L][H] = the uv / noise mix dsv_sine_source feeds its Linear, from that call's workspace (the unmixed sines), f0
+ *   and the noise draws, operation for operation.
+ * dsv_hgt_source_backward: har = tanh(l_linear(sines)): dw [H] = sum dp sines, db [1] = sum dp, dp = dhar (1 - har^2); float64, fixed order. */
+int32_t dsv_hgt_wgrad_split(void);
+int64_t dsv_hgt_act_floats(int32_t B, int32_t C, int32_t L);
+int64_t dsv_hgt_wgrad_workspace_floats(int32_t B, int32_t L, int32_t Co, int32_t Ci, int32_t K, int32_t up);
+int dsv_hgt_conv_dgrad(const float* g, const float* wt_packed, const float* x_saved, const float* residual, const float* sum_in, float* dx, int32_t B,
+                       int32_t Cg, int32_t C, int32_t K, int32_t pad, int32_t dil, int32_t L, float slope, float divide, void* stream);
+int dsv_hgt_conv_wgrad(const float* g, const float* x, float* workspace, int64_t workspace_floats, float* dw, int32_t B, int32_t Co, int32_t Ci,
+                       int32_t K, int32_t pad, int32_t dil, int32_t L, int32_t up, float slope, void* stream);
+int64_t dsv_hgt_bias_workspace_floats(int32_t B, int32_t C, int32_t L);
+int dsv_hgt_bias_grad(const float* g, float* workspace, int64_t workspace_floats, float* db, int32_t B, int32_t C, int32_t L, void* stream);
+int dsv_hgt_upsample_dgrad(const float* g, const float* w, const float* x_saved, float* dx, int32_t B, int32_t Ci, int32_t Co, int32_t up, int32_t K,
+                           int32_t L_in, float slope, float divide, void* stream);
+int dsv_hgt_tanh_backward(const float* gy, const float* y, float* out, int32_t B, int32_t L, void* stream);
+int dsv_hgt_noise_conv_backward(const float* g, const float* har, const float* w, float* workspace, int64_t workspace_floats, float* dw, float* db,
+                                float* dhar, int32_t B, int32_t C, int32_t K, int32_t stride, int32_t pad, int32_t L_har, int32_t L_out, int32_t first,
+                                void* stream);
+int dsv_hgt_source_mix(const float* f0, const float* sines_ws, const float* noise, float* sines, int32_t B, int32_t T, int32_t up, int32_t H,
+                       float sine_amp, float noise_std, float voiced_threshold, void* stream);
+int dsv_hgt_source_backward(const float* dhar, const float* har, const float* sines, float* dw, float* db, int32_t B, int32_t L, int32_t H,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
