@@ -45,7 +45,9 @@ def test_wgrad2_operator(B, T, Ci, Co, K, dil):
     assert e_w <= 2e-5 and e_b <= 2e-5
 
 
-def _make_stack(L, cycle, seed):
+def _make_stack(L, cycle, seed, dils=None):
+    """dils: an explicit list of dilations (then L = len(dils) and cycle is not read) instead of 2 ** (l % cycle)"""
+    L = len(dils) if dils is not None else L
     g = torch.Generator().manual_seed(seed)
     ws = {}
     ws['dc_w'] = [torch.randn(512, 256, 3, generator=g) * (256 * 3) ** -0.5 for _ in range(L)]
@@ -54,7 +56,7 @@ def _make_stack(L, cycle, seed):
     ws['cp_b'] = [torch.randn(512, generator=g) * 0.1 for _ in range(L)]
     ws['op_w'] = [torch.randn(512, 256, 1, generator=g) * 256 ** -0.5 for _ in range(L)]
     ws['op_b'] = [torch.randn(512, generator=g) * 0.1 for _ in range(L)]
-    dils = [2 ** (l % cycle) for l in range(L)]
+    dils = list(dils) if dils is not None else [2 ** (l % cycle) for l in range(L)]
     return ws, dils
 
 
@@ -106,11 +108,19 @@ def test_stack_forward_and_backward(B, T, L, cycle, stack_conv):
     """(the short shapes take the persistent forward: with the Winograd convolution, csrc/train_loop_wino.hpp, and with the direct one; the
     utterance of 8300 frames = 260 tiles does not fit the co-resident grid of a 256-CU part: per-layer forward launches, and the Winograd /
     direct data-gradient kernels behind them)"""
+    ws, dils = _make_stack(L, cycle, seed=L + T)
+    _check_stack_forward_and_backward(B, T, ws, dils, stack_conv)
+
+
+def _check_stack_forward_and_backward(B, T, ws, dils, stack_conv):
+    """forward (skip sum, saved y / a) and every gradient of the fused stack against float64 autograd; where a layer's dilation is >= T its
+    outer taps never meet the signal: their weight gradients are sums of products with a zero factor - exactly 0 as tap products ('direct',
+    'wino-taps'), within the tolerance in the Winograd dual form"""
     from diffsinger_amd import _lib, fs2, train_fused
     lib = _lib.load()
     train_fused._bind(lib)
     assert train_fused.stack_conv() == ('wino' if stack_conv == 'wino-taps' else stack_conv)
-    ws, dils = _make_stack(L, cycle, seed=L + T)
+    L = len(dils)
     g = torch.Generator().manual_seed(5 + T)
     x0 = torch.relu(torch.randn(B, 256, T, generator=g))
     cond = torch.randn(B, 256, T, generator=g)
@@ -168,6 +178,31 @@ def test_stack_forward_and_backward(B, T, L, cycle, stack_conv):
     if bad:
         print('  layers over tolerance: ' + ', '.join(f'{k}[{l}] {e:.1e}' for k, l, e in bad[:40]))
     assert all(v <= 2e-5 for v in errs.values()), errs
+    for l in range(L):
+        if dils[l] >= T:
+            gw, gr = wd[order.index('dc_w') * L + l].grad, r['dc_w'][l].grad
+            assert float(gr[:, :, 0].abs().max()) == 0 and float(gr[:, :, 2].abs().max()) == 0
+            outer = max(float(gw[:, :, 0].abs().max()), float(gw[:, :, 2].abs().max()))
+            print(f'  layer {l} (dilation {dils[l]} >= T = {T}): outer-tap weight gradients max {outer:.2e} ({stack_conv})')
+            assert outer <= (2e-5 * float(gr.abs().max()) if stack_conv == 'wino' else 0.0), (l, outer)
+
+
+@pytest.mark.parametrize('stack_conv', ['wino', 'wino-taps', 'direct'], indirect=True)
+@pytest.mark.parametrize('T,dils,per_layer', [(1, [8], False), (5, [8], False), (5, [8], True), (8, [8], False), (9, [8], False), (7, [4, 8], False),
+                                              (31, [4, 8], False), (32, [4, 8], False), (33, [4, 8], False), (33, [4, 8], True),
+                                              (17, [8, 1, 8], False), (65, [2, 8, 4], False)])
+def test_stack_forward_and_backward_short_lengths(T, dils, per_layer, stack_conv):
+    """The body of test_stack_forward_and_backward where the convolution's taps and Winograd pairs meet the end of the utterance: T <= d,
+    T <= 2 d, the frames on either side of a tile boundary, d = 8 as the first layer; B = 3 (the middle utterance has a neighbour on both sides
+    of the tile list).  per_layer: the forward as one launch per layer (dsf_set_stack_mode(0)) instead of the persistent kernel."""
+    from diffsinger_amd import train_fused
+    B = 3
+    ws, dils = _make_stack(None, None, seed=100 * len(dils) + T, dils=dils)
+    train_fused.set_stack_mode(0 if per_layer else 1)
+    try:
+        _check_stack_forward_and_backward(B, T, ws, dils, stack_conv)
+    finally:
+        train_fused.set_stack_mode(1)
 
 
 @pytest.mark.parametrize('B,T,L,cycle,dcond', [(9, 1000, 3, 4, False), (2, 50, 3, 4, True), (3, 96, 20, 4, False), (1, 5, 1, 1, True), (17, 500, 2, 2, True),
