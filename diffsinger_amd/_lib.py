@@ -319,3 +319,16 @@ def check(rc: int, what: str = ''):
     if rc != 0:
         msg = load().dsd_last_error()
         raise RuntimeError(f'{what or "libdsdenoise"} failed ({rc}): {msg.decode() if msg else "?"}')
+
+
+def call(name: str, dev, *args):
+    """Entry point `name` on device `dev`: the arguments, then that device's current stream as the last one; raises on a refusal."""
+    import torch
+    lib = load()
+    with torch.cuda.device(dev):
+        check(getattr(lib, name)(*args, torch.cuda.current_stream(dev).cuda_stream), name)
+
+
+def ptr(t):
+    """a tensor's address, None (a null pointer) for None"""
+    return t.data_ptr() if t is not None else None

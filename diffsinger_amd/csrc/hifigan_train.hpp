@@ -8,23 +8,20 @@
 //   k_hgt_dgrad       dx = (m (*) sum_o sum_k w[o][i][k] g[t - k dil + pad] + residual + sum_in) / divide, m = x_saved > 0 ? 1 : slope: a stride-1
 //                     convolution of g with the flipped, transposed filter (W'[i][o][k'] = w[o][i][K - 1 - k'], padding (K - 1) dil - pad) -
 //                     k_voc_conv's staging, chunk order and GemmPipe, its own epilogue.  A new kernel: no k_voc_conv instantiation changes.
-//   k_hgt_wgrad       dW [rows][K][Ci] = sum_t P(t) Q(t)^T over one split of kHgtSplit samples of one batch row, 128 rows and 64 columns per
-//                     workgroup (the k_pwgt_wgrad pattern): P = g (a transposed convolution: its polyphase rows co * u + phase at the input
-//                     rate), Q column k * Ci + ci = lrelu(x[ci][t + k dil - pad]), the leaky ReLU applied while staging.  k_pwgt_reduce adds the
-//                     splits in index order in float64.
+//   k_hgt_wgrad       dW [rows][K][Ci] = sum_t P(t) Q(t)^T over one split of kSplitK samples of one batch row, 128 rows and 64 columns per
+//                     workgroup (k_pwgt_wgrad's tile and step, constants in voc_train_common.hpp).  P = g (a transposed convolution: its
+//                     polyphase rows co * u + phase at the input rate), Q column k * Ci + ci = lrelu(x[ci][t + k dil - pad]), the leaky ReLU
+//                     applied while staging.  k_split_reduce (voc_train_common.hpp) adds the splits in index order in float64.
 //   k_hgt_up_dgrad    transposed convolution, data gradient: dx[ci][q] = m sum_co sum_j w[ci][co][j] g[co][q u + j - p] / divide (a gather)
 //   k_hgt_rowsum_part + _reduce / _tanh_bwd / _noise_wgrad / _noise_dhar / _source_mix / _source_bwd
 //                     the bias gradients, the output tanh, the noise convolutions and the source module: plain vector-ALU kernels, float64 sums
-//                     in a fixed order.
+//                     in a fixed order (block_sum of voc_train_common.hpp).
 // No atomics; every sum runs in a fixed order: two calls are bitwise equal.
 #pragma once
 #include "voc_kernels.hpp"
-#include "pwg_train.hpp"
+#include "voc_train_common.hpp"
 
 namespace dsd {
-
-constexpr int kHgtSplit = 512;                               // samples (at the rate of the convolution's input) per workgroup of k_hgt_wgrad
-constexpr int kHgtLdw = 33;                                  // LDS row stride of k_hgt_wgrad's tiles
 
 // ---- convolution data gradient with the mask epilogue -------------------------------------------------------------------------------------
 struct HgtDgradParams {
@@ -135,13 +132,13 @@ struct HgtWgradParams {
 };
 
 __global__ __launch_bounds__(kThreads, 2) void k_hgt_wgrad(const HgtWgradParams p) {
-    __shared__ float pt[128 * kHgtLdw];
-    __shared__ float qt[64 * kHgtLdw];
+    __shared__ float pt[128 * kSplitLdw];
+    __shared__ float qt[64 * kSplitLdw];
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int split = blockIdx.x, gc = blockIdx.y, row0 = blockIdx.z * 128;
-    const int b = split / p.nch, s0 = (split - b * p.nch) * kHgtSplit;
-    const int s1 = min(p.L, s0 + kHgtSplit);
+    const int b = split / p.nch, s0 = (split - b * p.nch) * kSplitK;
+    const int s1 = min(p.L, s0 + kSplitK);
     const int col = tid & 31, r0 = tid >> 5;
     const bool live = row0 + 32 * w < p.rows;                         // wave-uniform: rows past the matrix multiply nothing
     f32x16 acc[2];
@@ -185,18 +182,18 @@ __global__ __launch_bounds__(kThreads, 2) void k_hgt_wgrad(const HgtWgradParams 
         }
         __syncthreads();                                              // the previous chunk's LDS reads are done
 #pragma unroll
-        for (int i = 0; i < 16; ++i) pt[(r0 + 8 * i) * kHgtLdw + col] = pv[i];
+        for (int i = 0; i < 16; ++i) pt[(r0 + 8 * i) * kSplitLdw + col] = pv[i];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) qt[(r0 + 8 * i) * kHgtLdw + col] = qv[i];
+        for (int i = 0; i < 8; ++i) qt[(r0 + 8 * i) * kSplitLdw + col] = qv[i];
         __syncthreads();
         if (live) {
-            const float* ap = pt + (32 * w + j) * kHgtLdw + h;        // A[i = row][k = t]: lane half h supplies t = 2 s + h
-            const float* bp = qt + j * kHgtLdw + h;                   // B[k = t][j = column]
+            const float* ap = pt + (32 * w + j) * kSplitLdw + h;        // A[i = row][k = t]: lane half h supplies t = 2 s + h
+            const float* bp = qt + j * kSplitLdw + h;                   // B[k = t][j = column]
 #pragma unroll 4
             for (int s2 = 0; s2 < 16; ++s2) {
                 const float a = ap[2 * s2];
                 acc[0] = mfma32(a, bp[2 * s2], acc[0]);
-                acc[1] = mfma32(a, bp[32 * kHgtLdw + 2 * s2], acc[1]);
+                acc[1] = mfma32(a, bp[32 * kSplitLdw + 2 * s2], acc[1]);
             }
         }
     }
@@ -221,33 +218,21 @@ __global__ __launch_bounds__(kThreads, 2) void k_hgt_wgrad(const HgtWgradParams 
 constexpr int kHgtSumChunk = 1024;
 
 __global__ __launch_bounds__(256) void k_hgt_rowsum_part(const float* __restrict__ g, double* __restrict__ part, int C, int L, int LS, int nch) {
-    __shared__ double red[256];
     const int tid = threadIdx.x, chunk = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
     const int t0 = chunk * kHgtSumChunk, t1 = min(L, t0 + kHgtSumChunk);
     const float* gr = g + ((size_t)b * C + c) * LS;
     double s = 0.0;
     for (int t = t0 + tid; t < t1; t += 256) s += (double)gr[t];
-    red[tid] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] += red[tid + st];
-        __syncthreads();
-    }
-    if (tid == 0) part[((size_t)c * gridDim.z + b) * nch + chunk] = red[0];
+    s = block_sum(s);
+    if (tid == 0) part[((size_t)c * gridDim.z + b) * nch + chunk] = s;
 }
 
 __global__ __launch_bounds__(256) void k_hgt_rowsum_reduce(const double* __restrict__ part, float* __restrict__ out, int n) {
-    __shared__ double red[256];
     const int tid = threadIdx.x, c = blockIdx.x;
     double s = 0.0;
     for (int i = tid; i < n; i += 256) s += part[(size_t)c * n + i];
-    red[tid] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] += red[tid + st];
-        __syncthreads();
-    }
-    if (tid == 0) out[c] = (float)red[0];
+    s = block_sum(s);
+    if (tid == 0) out[c] = (float)s;
 }
 
 // transposed convolution (stride u, kernel k, padding p) behind a leaky ReLU, data gradient: a stride-u gather of g, ascending (co, j)
@@ -289,7 +274,6 @@ __global__ __launch_bounds__(256) void k_hgt_tanh_bwd(const float* __restrict__ 
 // dw[c][j] = sum_b sum_n g[b][c][n] har[b][n s - pad + j] in float64 (a thread walks ascending (b, n), then a fixed tree)
 __global__ __launch_bounds__(256) void k_hgt_noise_wgrad(const float* __restrict__ g, const float* __restrict__ har, float* __restrict__ dw, int B, int C,
                                                          int K, int s, int pad, int Lh, int LSh, int Lo, int LSo) {
-    __shared__ double red[256];
     const int tid = threadIdx.x, jj = blockIdx.x, c = blockIdx.y;
     double sum = 0.0;
     for (int b = 0; b < B; ++b) {
@@ -300,13 +284,8 @@ __global__ __launch_bounds__(256) void k_hgt_noise_wgrad(const float* __restrict
             if (i >= 0 && i < Lh) sum += (double)gr[n] * (double)hb[i];
         }
     }
-    red[tid] = sum;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] += red[tid + st];
-        __syncthreads();
-    }
-    if (tid == 0) dw[(size_t)c * K + jj] = (float)red[0];
+    sum = block_sum(sum);
+    if (tid == 0) dw[(size_t)c * K + jj] = (float)sum;
 }
 
 // its data gradient, accumulated over the stages: dhar[b][i] (+)= sum_c sum_n w[c][i + pad - n s] g[b][c][n], ascending (c, n)
@@ -357,7 +336,6 @@ __global__ __launch_bounds__(256) void k_hgt_source_mix(const HgtMixParams p) {
 // float64: a thread walks ascending (b, i), then a fixed tree.
 __global__ __launch_bounds__(256) void k_hgt_source_bwd(const float* __restrict__ dhar, const float* __restrict__ har, const float* __restrict__ sines,
                                                         float* __restrict__ dw, float* __restrict__ db, int B, int L, int LS, int H) {
-    __shared__ double red[256];
     const int tid = threadIdx.x, hh = blockIdx.x;
     double s = 0.0;
     for (int b = 0; b < B; ++b)
@@ -366,13 +344,8 @@ __global__ __launch_bounds__(256) void k_hgt_source_bwd(const float* __restrict_
             const double dp = (double)dhar[(size_t)b * LS + i] * (1.0 - hv * hv);
             s += (hh < H) ? dp * (double)sines[((size_t)b * L + i) * H + hh] : dp;
         }
-    red[tid] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] += red[tid + st];
-        __syncthreads();
-    }
-    if (tid == 0) { if (hh < H) dw[hh] = (float)red[0]; else db[0] = (float)red[0]; }
+    s = block_sum(s);
+    if (tid == 0) { if (hh < H) dw[hh] = (float)s; else db[0] = (float)s; }
 }
 
 }  // namespace dsd

@@ -18,11 +18,12 @@
 //                       (the form of k_fs_wgrad at half its rows - that kernel's 128-row tile and fixed 16 splits would put the discriminator's
 //                       weight gradient on 16 workgroups); partials to a workspace, k_pwgd_wgrad_reduce adds the splits in a fixed order (float64).
 //   k_pwgd_first / _last / _first_dx / _last_dgrad / _edge_wgrad / _edge_reduce       the 1 -> 64 and 64 -> 1 layers: plain vector-ALU kernels.
-//   k_pwgd_lsgan_partial / _final / _backward        mean((d - c)^2): float64 partial sums in a fixed order, a one-workgroup reduction; backward
+//   k_pwgd_lsgan_partial / _final / _backward        mean((d - c)^2): float64 partial sums in a fixed order (block_sum), a one-workgroup reduction; backward
 //                       2 (d - c) / n * g with g read from device memory.
 // No atomics, every sum in a fixed order: two calls are bitwise equal.
 #pragma once
 #include "voc_kernels.hpp"
+#include "voc_train_common.hpp"
 
 namespace dsd {
 
@@ -299,7 +300,6 @@ __global__ __launch_bounds__(256) void k_pwgd_first_dx(const float* __restrict__
 // float64 sums: a thread walks its samples in ascending order, then a fixed tree.
 __global__ __launch_bounds__(256) void k_pwgd_edge_wgrad(const float* __restrict__ P, const float* __restrict__ Q, float* __restrict__ part, int T,
                                                          size_t bs_p, size_t cs_p, size_t bs_q, size_t cs_q, int nch) {
-    __shared__ double red[4][256];
     const int tid = threadIdx.x, c = blockIdx.x, split = blockIdx.y, b = split / nch, s0 = (split - b * nch) * kPwgdEdgeSplit;
     const int s1 = min(T, s0 + kPwgdEdgeSplit);
     const float* pr = P + (size_t)b * bs_p + (size_t)c * cs_p;
@@ -310,17 +310,11 @@ __global__ __launch_bounds__(256) void k_pwgd_edge_wgrad(const float* __restrict
         const float qm = t > 0 ? qr[t - 1] : 0.f, qp = t + 1 < T ? qr[t + 1] : 0.f;
         s[0] += pv * (double)qm; s[1] += pv * (double)qr[t]; s[2] += pv * (double)qp; s[3] += pv;
     }
+    block_sum(s);
+    if (tid == 0) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) red[k][tid] = s[k];
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red[k][tid] += red[k][tid + st];
-        }
-        __syncthreads();
+        for (int k = 0; k < 4; ++k) part[((size_t)split * kPwgdC + c) * 4 + k] = (float)s[k];
     }
-    if (tid < 4) part[((size_t)split * kPwgdC + c) * 4 + tid] = (float)red[tid][0];
 }
 
 // dw [64][3]; db [64] (per_channel_bias) or db [1] = channel 0's sum (the last layer: every channel's workgroups summed the same gp); db may be nullptr
@@ -336,32 +330,20 @@ __global__ __launch_bounds__(256) void k_pwgd_edge_reduce(const float* __restric
 // ---- LSGAN --------------------------------------------------------------------------------------------------------------------------------
 constexpr int kPwgdLossThreads = 256, kPwgdLossMaxBlocks = 1024;
 
-__device__ __forceinline__ double pwgd_block_sum(double a) {
-    __shared__ double red[kPwgdLossThreads];
-    const int tid = threadIdx.x;
-    red[tid] = a;
-    __syncthreads();
-    for (int s = kPwgdLossThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __global__ void __launch_bounds__(kPwgdLossThreads) k_pwgd_lsgan_partial(const float* d, float c, double* ws, long long n) {
     double s = 0.0;
     for (long long i = (long long)blockIdx.x * kPwgdLossThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kPwgdLossThreads) {
         const double e = (double)d[i] - (double)c;
         s += e * e;
     }
-    s = pwgd_block_sum(s);
+    s = block_sum<kPwgdLossThreads>(s);
     if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 
 __global__ void __launch_bounds__(kPwgdLossThreads) k_pwgd_lsgan_final(const double* ws, float* out, int nblocks, long long n) {
     double s = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += kPwgdLossThreads) s += ws[i];
-    s = pwgd_block_sum(s);
+    s = block_sum<kPwgdLossThreads>(s);
     if (threadIdx.x == 0) out[0] = (float)(s / (double)n);
 }
 

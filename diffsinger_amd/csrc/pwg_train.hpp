@@ -14,8 +14,9 @@
 //   k_pwgt_conv_bwd   dx = s dx' + sum_tap W_conv[:, :, tap]^T da(t - (tap - 1) d): the forward's "taps are rows of one staged tile" with three
 //                     da tiles fetched at their own offsets (K = 384 -> 64 rows, again two K halves), and from the centre tile the running
 //                     conditioning gradient dC (+)= W_aux^T da (K = 128 -> aux rows) with a `first` flag like the forward's skip sum.
-//   k_pwgt_wgrad      dW [128][N] = sum_t P(t) Q(t)^T and db = sum_t P over one split of kPwgtSplit samples of one batch row and one group of
-//                     64 columns per workgroup (the k_pwgd_wgrad pattern); k_pwgt_reduce adds the splits in index order in float64.
+//   k_pwgt_wgrad      dW [128][N] = sum_t P(t) Q(t)^T and db = sum_t P over one split of kSplitK samples of one batch row and one group of
+//                     64 columns per workgroup (the tile k_hgt_wgrad runs too); k_split_reduce (voc_train_common.hpp) adds the splits in index
+//                     order in float64.
 //                       block conv + aux:   P = da,            Q = [x(t - d); x(t); x(t + d); c(t)]     N = 192 + aux
 //                       block out + skip:   P = [s dx'; dS],   Q = z(t) recomputed from a_l              N = 64
 //                       last_conv_layers[1]: P = [g; 0],       Q = relu(saved)                           N = 64
@@ -24,11 +25,9 @@
 // No atomics; every sum runs in a fixed order: two calls are bitwise equal.
 #pragma once
 #include "pwg_kernels.hpp"
+#include "voc_train_common.hpp"
 
 namespace dsd {
-
-constexpr int kPwgtSplit = 512;                              // samples per workgroup of k_pwgt_wgrad
-constexpr int kPwgtLdw = 33;                                 // LDS row stride of k_pwgt_wgrad's tiles
 
 // tanh(a) and sigmoid(g) exactly as k_pwg_layer evaluates them
 __device__ __forceinline__ float pwgt_tanh(float xa) { return 1.f - 2.f / (__expf(2.f * xa) + 1.f); }
@@ -318,13 +317,13 @@ struct PwgtWgradParams {
 };
 
 __global__ __launch_bounds__(kThreads, 2) void k_pwgt_wgrad(const PwgtWgradParams p) {
-    __shared__ float pt[kPwgGate * kPwgtLdw];
-    __shared__ float qt[kPwgRes * kPwgtLdw];
+    __shared__ float pt[kPwgGate * kSplitLdw];
+    __shared__ float qt[kPwgRes * kSplitLdw];
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int split = blockIdx.x, g = blockIdx.y;
-    const int b = split / p.nch, s0 = (split - b * p.nch) * kPwgtSplit;
-    const int s1 = min(p.L, s0 + kPwgtSplit);
+    const int b = split / p.nch, s0 = (split - b * p.nch) * kSplitK;
+    const int s1 = min(p.L, s0 + kSplitK);
     const int col = tid & 31, r0 = tid >> 5;
     const bool live = (w < 2) ? (p.p0 != nullptr) : (p.p1 != nullptr);       // wave-uniform: a missing half of P multiplies nothing
     f32x16 acc[2];
@@ -379,21 +378,21 @@ __global__ __launch_bounds__(kThreads, 2) void k_pwgt_wgrad(const PwgtWgradParam
         __syncthreads();                                              // the previous chunk's LDS reads are done
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            pt[(r0 + 8 * i) * kPwgtLdw + col] = pv[i];
-            pt[(kPwgRes + r0 + 8 * i) * kPwgtLdw + col] = pv[8 + i];
-            qt[(r0 + 8 * i) * kPwgtLdw + col] = qv[i];
+            pt[(r0 + 8 * i) * kSplitLdw + col] = pv[i];
+            pt[(kPwgRes + r0 + 8 * i) * kSplitLdw + col] = pv[8 + i];
+            qt[(r0 + 8 * i) * kSplitLdw + col] = qv[i];
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) bsum[i] += pv[i];
         __syncthreads();
         if (live) {
-            const float* ap = pt + (32 * w + j) * kPwgtLdw + h;       // A[i = row][k = t]: lane half h supplies t = 2 s + h
-            const float* bp = qt + j * kPwgtLdw + h;                  // B[k = t][j = column]
+            const float* ap = pt + (32 * w + j) * kSplitLdw + h;       // A[i = row][k = t]: lane half h supplies t = 2 s + h
+            const float* bp = qt + j * kSplitLdw + h;                  // B[k = t][j = column]
 #pragma unroll 4
             for (int s2 = 0; s2 < 16; ++s2) {
                 const float a = ap[2 * s2];
                 acc[0] = mfma32(a, bp[2 * s2], acc[0]);
-                acc[1] = mfma32(a, bp[32 * kPwgtLdw + 2 * s2], acc[1]);
+                acc[1] = mfma32(a, bp[32 * kSplitLdw + 2 * s2], acc[1]);
             }
         }
     }
@@ -417,24 +416,13 @@ __global__ __launch_bounds__(kThreads, 2) void k_pwgt_wgrad(const PwgtWgradParam
     }
 }
 
-// out[i] = sum_k part[k * n + i] in float64, ascending k, rounded once
-__global__ __launch_bounds__(256) void k_pwgt_reduce(const float* __restrict__ part, float* __restrict__ out, int n, int nsplit) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    double s = 0.0;
-#pragma unroll 8
-    for (int k = 0; k < nsplit; ++k) s += (double)part[(size_t)k * n + i];
-    out[i] = (float)s;
-}
-
 // ---- vector-shaped pieces -------------------------------------------------------------------------------------------------------------------
 // out[2 c] = sum_b sum_t P[b][c][t] q(Q[b][c][t]), out[2 c + 1] = sum_b sum_t P[b][c][t]; a row of P / Q is shared by every channel when its
 // channel stride is 0; q = relu when relu_q.  float64: a thread walks its samples in ascending (b, t), then a fixed tree.
 __global__ __launch_bounds__(256) void k_pwgt_rowdot(const float* __restrict__ P, const float* __restrict__ Q, float* __restrict__ out, int B, int L,
                                                      size_t bs_p, size_t cs_p, size_t bs_q, size_t cs_q, int relu_q) {
-    __shared__ double red[2][256];
     const int tid = threadIdx.x, c = blockIdx.x;
-    double s0 = 0.0, s1 = 0.0;
+    double s[2] = {0.0, 0.0};
     for (int b = 0; b < B; ++b) {
         const float* pr = P + (size_t)b * bs_p + (size_t)c * cs_p;
         const float* qr = Q + (size_t)b * bs_q + (size_t)c * cs_q;
@@ -442,17 +430,12 @@ __global__ __launch_bounds__(256) void k_pwgt_rowdot(const float* __restrict__ P
             const double pv = (double)pr[t];
             float qv = qr[t];
             if (relu_q) qv = qv > 0.f ? qv : 0.f;
-            s0 += pv * (double)qv;
-            s1 += pv;
+            s[0] += pv * (double)qv;
+            s[1] += pv;
         }
     }
-    red[0][tid] = s0; red[1][tid] = s1;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) { red[0][tid] += red[0][tid + st]; red[1][tid] += red[1][tid + st]; }
-        __syncthreads();
-    }
-    if (tid < 2) out[2 * c + tid] = (float)red[tid][0];
+    block_sum(s);
+    if (tid == 0) { out[2 * c] = (float)s[0]; out[2 * c + 1] = (float)s[1]; }
 }
 
 // data gradient of the 64 -> 1 output convolution through the ReLU in front of it: out[b][c][t] = w[c] g[b][t] where saved[b][c][t] > 0
@@ -501,7 +484,6 @@ __global__ __launch_bounds__(256) void k_pwgt_up_dgrad(const float* __restrict__
 // filter gradient, per row: part[r][j] = sum_t g[r][t] in[r][(t + j - scale) / scale] in float64 (a thread walks ascending t, then a fixed tree)
 __global__ __launch_bounds__(256) void k_pwgt_up_wgrad(const float* __restrict__ g, const float* __restrict__ in, double* __restrict__ part, int L_in,
                                                        int LS_in, int scale, int LS_out) {
-    __shared__ double red[256];
     const int tid = threadIdx.x, jj = blockIdx.x;
     const size_t r = blockIdx.y;
     const int L_out = L_in * scale;
@@ -512,13 +494,8 @@ __global__ __launch_bounds__(256) void k_pwgt_up_wgrad(const float* __restrict__
         const int u = t + jj - scale;
         if (u >= 0 && u < L_out) s += (double)gr[t] * (double)ir[u / scale];
     }
-    red[tid] = s;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] += red[tid + st];
-        __syncthreads();
-    }
-    if (tid == 0) part[r * (2 * scale + 1) + jj] = red[0];
+    s = block_sum(s);
+    if (tid == 0) part[r * (2 * scale + 1) + jj] = s;
 }
 
 // dw[j] = sum_r part[r][j], ascending r

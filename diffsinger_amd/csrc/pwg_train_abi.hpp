@@ -2,17 +2,12 @@
 // pwg_train.hpp); included at the end of dsd.hip behind pwg_disc_abi.hpp.  Every entry point validates on the host and refuses with
 // DSD_ERR_INVALID before any launch; nothing allocates or synchronises.
 #include "pwg_train.hpp"
+#include "voc_train_host.hpp"
 
-extern "C" int32_t dsv_pwgt_wgrad_split(void) { return kPwgtSplit; }
+extern "C" int32_t dsv_pwgt_wgrad_split(void) { return kSplitK; }
 
-static bool pwgt_shape_ok(int B, int L) { return B >= 1 && B <= 65535 && L >= 1 && L <= (1 << 30); }
 static bool pwgt_aux_ok(int naux) { return naux >= 0 && naux <= kPwgMaxAux && (naux % 8) == 0; }
-static int pwgt_splits(int L) { return (L + kPwgtSplit - 1) / kPwgtSplit; }
 
-static int pwgt_check(const char* who, int B, int L) {
-    if (!pwgt_shape_ok(B, L)) return fail(DSD_ERR_INVALID, "%s: bad shape (B=%d in [1, 65535], L=%d in [1, 2^30])", who, B, L);
-    return DSD_OK;
-}
 static int pwgt_check_aux(const char* who, int naux, const void* c) {
     if (!pwgt_aux_ok(naux) || (naux && !c))
         return fail(DSD_ERR_INVALID, "%s: aux=%d must be a multiple of 8 in [0, %d] with its tensor present", who, naux, kPwgMaxAux);
@@ -20,8 +15,8 @@ static int pwgt_check_aux(const char* who, int naux, const void* c) {
 }
 
 extern "C" int64_t dsv_pwgt_wgrad_workspace_floats(int32_t B, int32_t L, int32_t n_cols) {
-    if (!pwgt_shape_ok(B, L) || n_cols < 8 || n_cols > 3 * kPwgRes + kPwgMaxAux || (n_cols % 8)) return -1;
-    return (int64_t)B * pwgt_splits(L) * ((int64_t)kPwgGate * n_cols + kPwgGate);
+    if (!voc_shape_ok(B, L) || n_cols < 8 || n_cols > 3 * kPwgRes + kPwgMaxAux || (n_cols % 8)) return -1;
+    return (int64_t)B * voc_splits(L, kSplitK) * ((int64_t)kPwgGate * n_cols + kPwgGate);
 }
 
 extern "C" int64_t dsv_pwgt_upsample_workspace_floats(int64_t rows, int32_t scale) {
@@ -34,7 +29,7 @@ extern "C" int dsv_pwgt_layer(const float* x, const float* c, const float* w1_pa
                               void* stream) {
     if (!x || !w1_packed || !w2_packed || !x_out || !skip || !a_out || x == x_out)
         return fail(DSD_ERR_INVALID, "dsv_pwgt_layer: null argument / in-place call");
-    DSD_TRY(pwgt_check("dsv_pwgt_layer", B, L));
+    DSD_TRY(voc_check_shape("dsv_pwgt_layer", B, L));
     DSD_TRY(pwgt_check_aux("dsv_pwgt_layer", n_aux, c));
     if (dil < 1) return fail(DSD_ERR_INVALID, "dsv_pwgt_layer: dil=%d must be positive", dil);
     if (first_on_device(41)) HIP_TRY(hipFuncSetAttribute((const void*)k_pwgt_layer, hipFuncAttributeMaxDynamicSharedMemorySize, kPwgLayerLdsBytes));
@@ -52,7 +47,7 @@ extern "C" int dsv_pwgt_layer(const float* x, const float* c, const float* w1_pa
 extern "C" int dsv_pwgt_gate_backward(const float* dx_next, const float* d_skip, const float* a, const float* w2t_packed, float* da, int32_t B,
                                       int32_t L, void* stream) {
     if (!d_skip || !a || !w2t_packed || !da) return fail(DSD_ERR_INVALID, "dsv_pwgt_gate_backward: null argument");
-    DSD_TRY(pwgt_check("dsv_pwgt_gate_backward", B, L));
+    DSD_TRY(voc_check_shape("dsv_pwgt_gate_backward", B, L));
     PwgtGateBwdParams p{};
     p.dxp = dx_next; p.ds = d_skip; p.a = a; p.w2tp = reinterpret_cast<const float4*>(w2t_packed); p.da = da; p.L = L; p.LS = voc_ls(L);
     hipLaunchKernelGGL(k_pwgt_gate_bwd, dim3((unsigned)(p.LS / 32), (unsigned)B), dim3(kThreads), 0, (hipStream_t)stream, p);
@@ -63,7 +58,7 @@ extern "C" int dsv_pwgt_gate_backward(const float* dx_next, const float* d_skip,
 extern "C" int dsv_pwgt_conv_backward(const float* da, const float* dx_next, const float* w1t_packed, const float* wauxt_packed, float* dx, float* dc,
                                       int32_t B, int32_t L, int32_t n_aux, int32_t dil, int32_t first, void* stream) {
     if (!da || !w1t_packed || !dx || dx == dx_next) return fail(DSD_ERR_INVALID, "dsv_pwgt_conv_backward: null argument / in-place call");
-    DSD_TRY(pwgt_check("dsv_pwgt_conv_backward", B, L));
+    DSD_TRY(voc_check_shape("dsv_pwgt_conv_backward", B, L));
     if (!pwgt_aux_ok(n_aux) || (n_aux && (!dc || !wauxt_packed)))
         return fail(DSD_ERR_INVALID, "dsv_pwgt_conv_backward: aux=%d must be a multiple of 8 in [0, %d] with dc and its matrix present", n_aux, kPwgMaxAux);
     if (dil < 1) return fail(DSD_ERR_INVALID, "dsv_pwgt_conv_backward: dil=%d must be positive", dil);
@@ -78,13 +73,13 @@ extern "C" int dsv_pwgt_conv_backward(const float* da, const float* dx_next, con
 
 // partials + reduction of one 128-row gradient; out = [128][N] then [128]
 static int pwgt_wgrad_launch(const char* who, PwgtWgradParams& p, float* workspace, float* out, int B, hipStream_t s) {
-    p.part = workspace; p.nch = pwgt_splits(p.L);
+    p.part = workspace; p.nch = voc_splits(p.L, kSplitK);
     const int64_t nsplit = (int64_t)B * p.nch;
     if (nsplit > 0x7fffffff / 2) return fail(DSD_ERR_INVALID, "%s: B * splits = %lld is too large", who, (long long)nsplit);
     const int n = kPwgGate * p.N + kPwgGate;
     hipLaunchKernelGGL(k_pwgt_wgrad, dim3((unsigned)nsplit, (unsigned)((p.N + 63) / 64)), dim3(kThreads), 0, s, p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_pwgt_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)workspace, out, n, (int)nsplit);
+    hipLaunchKernelGGL(k_split_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)workspace, out, n, (int)nsplit);
     HIP_TRY(hipGetLastError());
     return DSD_OK;
 }
@@ -92,7 +87,7 @@ static int pwgt_wgrad_launch(const char* who, PwgtWgradParams& p, float* workspa
 extern "C" int dsv_pwgt_wgrad_conv(const float* da, const float* x, const float* c, float* workspace, float* out, int32_t B, int32_t L, int32_t n_aux,
                                    int32_t dil, void* stream) {
     if (!da || !x || !workspace || !out) return fail(DSD_ERR_INVALID, "dsv_pwgt_wgrad_conv: null argument");
-    DSD_TRY(pwgt_check("dsv_pwgt_wgrad_conv", B, L));
+    DSD_TRY(voc_check_shape("dsv_pwgt_wgrad_conv", B, L));
     DSD_TRY(pwgt_check_aux("dsv_pwgt_wgrad_conv", n_aux, c));
     if (dil < 1) return fail(DSD_ERR_INVALID, "dsv_pwgt_wgrad_conv: dil=%d must be positive", dil);
     PwgtWgradParams p{};
@@ -105,7 +100,7 @@ extern "C" int dsv_pwgt_wgrad_conv(const float* da, const float* x, const float*
 extern "C" int dsv_pwgt_wgrad_out(const float* dx_next, const float* d_skip, const float* a, float* workspace, float* out, int32_t B, int32_t L,
                                   void* stream) {
     if (!d_skip || !a || !workspace || !out) return fail(DSD_ERR_INVALID, "dsv_pwgt_wgrad_out: null argument");
-    DSD_TRY(pwgt_check("dsv_pwgt_wgrad_out", B, L));
+    DSD_TRY(voc_check_shape("dsv_pwgt_wgrad_out", B, L));
     PwgtWgradParams p{};
     p.LS = voc_ls(L); p.L = L;
     // P rows follow the forward's second matrix: 0..63 conv1x1_out (s dx'), 64..127 conv1x1_skip (dS).  Without dx' (the last block) the out rows
@@ -117,7 +112,7 @@ extern "C" int dsv_pwgt_wgrad_out(const float* dx_next, const float* d_skip, con
 
 extern "C" int dsv_pwgt_wgrad_relu(const float* g, const float* saved, float* workspace, float* out, int32_t B, int32_t L, void* stream) {
     if (!g || !saved || !workspace || !out) return fail(DSD_ERR_INVALID, "dsv_pwgt_wgrad_relu: null argument");
-    DSD_TRY(pwgt_check("dsv_pwgt_wgrad_relu", B, L));
+    DSD_TRY(voc_check_shape("dsv_pwgt_wgrad_relu", B, L));
     PwgtWgradParams p{};
     p.LS = voc_ls(L); p.L = L;
     p.p0 = g; p.p1 = nullptr; p.bs0 = p.bs1 = (size_t)kPwgRes * p.LS; p.scale0 = 1.f;
@@ -128,7 +123,7 @@ extern "C" int dsv_pwgt_wgrad_relu(const float* g, const float* saved, float* wo
 extern "C" int dsv_pwgt_rowdot(const float* P, const float* Q, float* out, int32_t B, int32_t C, int32_t L, int32_t p_per_channel,
                                int32_t q_per_channel, int32_t relu_q, void* stream) {
     if (!P || !Q || !out) return fail(DSD_ERR_INVALID, "dsv_pwgt_rowdot: null argument");
-    DSD_TRY(pwgt_check("dsv_pwgt_rowdot", B, L));
+    DSD_TRY(voc_check_shape("dsv_pwgt_rowdot", B, L));
     if (C < 1 || C > 65535) return fail(DSD_ERR_INVALID, "dsv_pwgt_rowdot: C=%d must be in [1, 65535]", C);
     const size_t LS = (size_t)voc_ls(L);
     hipLaunchKernelGGL(k_pwgt_rowdot, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, P, Q, out, B, L, p_per_channel ? (size_t)C * LS : LS,
@@ -139,7 +134,7 @@ extern "C" int dsv_pwgt_rowdot(const float* P, const float* Q, float* out, int32
 
 extern "C" int dsv_pwgt_last_dgrad(const float* g, const float* saved, const float* w, float* out, int32_t B, int32_t C, int32_t L, void* stream) {
     if (!g || !saved || !w || !out) return fail(DSD_ERR_INVALID, "dsv_pwgt_last_dgrad: null argument");
-    DSD_TRY(pwgt_check("dsv_pwgt_last_dgrad", B, L));
+    DSD_TRY(voc_check_shape("dsv_pwgt_last_dgrad", B, L));
     if (C < 1 || C > 65535) return fail(DSD_ERR_INVALID, "dsv_pwgt_last_dgrad: C=%d must be in [1, 65535]", C);
     const int LS = voc_ls(L);
     hipLaunchKernelGGL(k_pwgt_last_dgrad, dim3((unsigned)((LS + 255) / 256), (unsigned)C, (unsigned)B), dim3(256), 0, (hipStream_t)stream, g, saved, w,
@@ -163,7 +158,7 @@ extern "C" int dsv_pwgt_upsample_backward(const float* g, const float* in, const
     if (!g || !in || !filter || !workspace || !dw) return fail(DSD_ERR_INVALID, "dsv_pwgt_upsample_backward: null argument");
     if (rows < 1 || rows > 65535 || L_in < 1 || scale < 1 || scale > 64 || (int64_t)L_in * scale > (1 << 30))
         return fail(DSD_ERR_INVALID, "dsv_pwgt_upsample_backward: bad shape (rows=%lld L=%d scale=%d)", (long long)rows, L_in, scale);
-    if ((uintptr_t)workspace & 7) return fail(DSD_ERR_INVALID, "dsv_pwgt_upsample_backward: the workspace must be aligned to 8 bytes (float64 sums)");
+    DSD_TRY(voc_check_f64_workspace("dsv_pwgt_upsample_backward", workspace));
     const int LS_in = voc_ls(L_in), LS_out = voc_ls(L_in * scale), ntap = 2 * scale + 1;
     double* ws = reinterpret_cast<double*>(workspace);
     hipLaunchKernelGGL(k_pwgt_up_wgrad, dim3((unsigned)ntap, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, g, in, ws, L_in, LS_in, scale, LS_out);
@@ -180,7 +175,7 @@ extern "C" int dsv_pwgt_upsample_backward(const float* g, const float* in, const
 
 extern "C" int dsv_pwgt_convin_wgrad(const float* g, const float* c, float* dw, int32_t B, int32_t C, int32_t K, int32_t L_out, void* stream) {
     if (!g || !c || !dw) return fail(DSD_ERR_INVALID, "dsv_pwgt_convin_wgrad: null argument");
-    DSD_TRY(pwgt_check("dsv_pwgt_convin_wgrad", B, L_out));
+    DSD_TRY(voc_check_shape("dsv_pwgt_convin_wgrad", B, L_out));
     if (C < 1 || C > kPwgMaxAux || K < 1 || K > 65) return fail(DSD_ERR_INVALID, "dsv_pwgt_convin_wgrad: bad shape (C=%d in [1, %d], K=%d in [1, 65])", C, kPwgMaxAux, K);
     const int n = C * C * K;
     hipLaunchKernelGGL(k_pwgt_convin_wgrad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, c, dw, B, C, K, L_out, voc_ls(L_out),

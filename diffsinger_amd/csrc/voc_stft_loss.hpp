@@ -20,7 +20,7 @@
 // A short row (pads < L is all the forward asks) has samples that are mirrored on both sides: the three terms are independent.
 //
 // SPECTRAL LOSS.  Forward: one pass over X and Y (float2 loads), per-thread float64 sums of (ym - xm)^2, ym^2, |ln ym - ln xm| over a
-// grid-stride walk, a fixed-order tree per workgroup, partials to a workspace; a one-workgroup second launch adds the partials in index
+// grid-stride walk, a fixed-order tree per workgroup (block_sum of voc_train_common.hpp), partials to a workspace; a one-workgroup second launch adds the partials in index
 // order (float64) and writes out[2] plus the two norms the backward needs.  Backward: element-wise,
 //     G = (re, im) * [ -g_sc (ym - xm) / (xm S1 S2) - g_mag sign(ln ym - ln xm) / (n P) ]        where P = re^2 + im^2 > 1e-7, else exactly 0
 // g_sc, g_mag read from device memory.  sign is taken from the clamped powers (the logarithm and the root are monotone); where ym == xm the
@@ -29,6 +29,7 @@
 #pragma once
 
 #include "voc_stft.hpp"
+#include "voc_train_common.hpp"
 
 namespace dsd {
 
@@ -83,47 +84,33 @@ __global__ void __launch_bounds__(256) k_stft_adj_fold(StftAdjFoldParams p) {
     p.out[(size_t)b * p.L + u] = sum;
 }
 
-// fixed-order sum of three per-thread doubles over the workgroup: thread 0 returns the totals
-__device__ __forceinline__ void stft_loss_block_sum(double& a, double& b, double& c) {
-    __shared__ double red[3][kStftLossThreads];
-    const int tid = threadIdx.x;
-    red[0][tid] = a; red[1][tid] = b; red[2][tid] = c;
-    __syncthreads();
-    for (int s = kStftLossThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; red[2][tid] += red[2][tid + s];
-        }
-        __syncthreads();
-    }
-    a = red[0][0]; b = red[1][0]; c = red[2][0];
-}
-
 __global__ void __launch_bounds__(kStftLossThreads) k_stft_loss_partial(const float2* X, const float2* Y, double* ws, long long n) {
-    double sd = 0.0, sy = 0.0, sl = 0.0;
+    double s[3] = {0.0, 0.0, 0.0};                                           // (ym - xm)^2, ym^2, |ln ym - ln xm|
     for (long long i = (long long)blockIdx.x * kStftLossThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kStftLossThreads) {
         const float2 x = X[i], y = Y[i];
         const float px = fmaxf(x.x * x.x + x.y * x.y, kStftLossClamp), py = fmaxf(y.x * y.x + y.y * y.y, kStftLossClamp);
         const float xm = sqrtf(px), ym = sqrtf(py);
         const float d = ym - xm;
-        sd += (double)d * (double)d;
-        sy += (double)ym * (double)ym;
-        sl += (double)fabsf(logf(ym) - logf(xm));
+        s[0] += (double)d * (double)d;
+        s[1] += (double)ym * (double)ym;
+        s[2] += (double)fabsf(logf(ym) - logf(xm));
     }
-    stft_loss_block_sum(sd, sy, sl);
+    block_sum<3, kStftLossThreads>(s);
     if (threadIdx.x == 0) {
         double* o = ws + kStftLossHead + 3 * (size_t)blockIdx.x;
-        o[0] = sd; o[1] = sy; o[2] = sl;
+        o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
     }
 }
 
 __global__ void __launch_bounds__(kStftLossThreads) k_stft_loss_final(double* ws, float* out, int nblocks, long long n) {
-    double sd = 0.0, sy = 0.0, sl = 0.0;
+    double s[3] = {0.0, 0.0, 0.0};
     for (int i = threadIdx.x; i < nblocks; i += kStftLossThreads) {
         const double* q = ws + kStftLossHead + 3 * (size_t)i;
-        sd += q[0]; sy += q[1]; sl += q[2];
+        s[0] += q[0]; s[1] += q[1]; s[2] += q[2];
     }
-    stft_loss_block_sum(sd, sy, sl);
+    block_sum<3, kStftLossThreads>(s);
     if (threadIdx.x == 0) {
+        const double sd = s[0], sy = s[1], sl = s[2];
         const double s1 = sqrt(sd), s2 = sqrt(sy);
         ws[0] = s1; ws[1] = s2; ws[2] = sl; ws[3] = (double)n;
         out[0] = (float)(s1 / s2);                                           // s2 >= sqrt(n * 1e-7) > 0: the clamp

@@ -2,6 +2,7 @@
 // the end of dsd.hip behind voc_stft_abi.hpp (shares stft_nfft_ok, stft_fill, stft_plan, stft_zsplit).  Every entry point
 // validates on the host and refuses with DSD_ERR_INVALID before any launch; nothing allocates or synchronises.
 #include "voc_stft_loss.hpp"
+#include "voc_train_host.hpp"
 
 // site id of first_on_device in this file: 703.  It sets the dynamic-LDS attribute of k_stft<2, 2> - the SAME function object site 702 (dsv_istft,
 // voc_stft_abi.hpp) sets: both stay, because either entry point can be the first caller of the kernel on a device.
@@ -57,8 +58,7 @@ extern "C" int64_t dsv_spectral_loss_workspace_floats(int64_t n) {
 static int stft_loss_check(const char* who, const void* a, const void* b, const void* c, const void* d, int64_t n) {
     if (!a || !b || !c || !d) return fail(DSD_ERR_INVALID, "%s: null argument", who);
     if (n < 1 || n > ((int64_t)1 << 40)) return fail(DSD_ERR_INVALID, "%s: bad shape (n=%lld complex elements must be in [1, 2^40])", who, (long long)n);
-    if ((uintptr_t)c & 7) return fail(DSD_ERR_INVALID, "%s: the workspace must be aligned to 8 bytes (it holds float64 sums)", who);
-    return DSD_OK;
+    return voc_check_f64_workspace(who, c, "it holds float64 sums");
 }
 
 extern "C" int dsv_spectral_loss(const float* X, const float* Y, float* workspace, float* out, int64_t n, void* stream) {

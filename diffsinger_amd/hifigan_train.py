@@ -15,8 +15,6 @@ everything is enqueued on the current stream in one order: forward, objective an
 Every sum runs in a fixed order: two steps on the same inputs are bitwise equal."""
 from __future__ import annotations
 
-from typing import Optional
-
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
@@ -36,16 +34,6 @@ def _ops() -> _HipOps:
     if _OPS[0] is None:
         _OPS[0] = _HipOps()
     return _OPS[0]
-
-
-def _call(name, dev, *args):
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, torch.cuda.current_stream(dev).cuda_stream), name)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
 
 
 def _floats(dev, n: int) -> torch.Tensor:
@@ -134,10 +122,10 @@ class HifiGanGenFunction(torch.autograd.Function):
             sw = torch.empty(B, H, Lh, device=dev, dtype=torch.float32)
             har = _act(dev, B, 1, Lh).view(B, -1)
             lw, lb = pd['m_source.l_linear.']
-            _call('dsv_sine_source', dev, f0c.data_ptr(), ri.data_ptr(), nz.data_ptr(), lw.reshape(-1).data_ptr(), lb.data_ptr(), sw.data_ptr(),
+            _lib.call('dsv_sine_source', dev, f0c.data_ptr(), ri.data_ptr(), nz.data_ptr(), lw.reshape(-1).data_ptr(), lb.data_ptr(), sw.data_ptr(),
                   har.data_ptr(), B, T, hop, H, float(h['audio_sample_rate']), SINE_AMP, NOISE_STD, VOICED_THRESHOLD)
             sines = torch.empty(B, Lh, H, device=dev, dtype=torch.float32)
-            _call('dsv_hgt_source_mix', dev, f0c.data_ptr(), sw.data_ptr(), nz.data_ptr(), sines.data_ptr(), B, T, hop, H, SINE_AMP, NOISE_STD,
+            _lib.call('dsv_hgt_source_mix', dev, f0c.data_ptr(), sw.data_ptr(), nz.data_ptr(), sines.data_ptr(), B, T, hop, H, SINE_AMP, NOISE_STD,
                   VOICED_THRESHOLD)
         L = T
         y = _fconv(ops, xin, L, *pd['conv_pre.'])
@@ -221,22 +209,22 @@ class HifiGanGenFunction(torch.autograd.Function):
             co, ci, k = (w.shape if w is not None else (g.shape[1], xs.shape[1], 7))
             pad = get_padding(k, dil)
             dwk = _floats(dev, co * k * ci)
-            _call('dsv_hgt_conv_wgrad', dev, g.data_ptr(), xs.data_ptr(), ws.data_ptr(), ws.numel(), dwk.data_ptr(), B, co, ci, k, pad, dil, L, 1,
+            _lib.call('dsv_hgt_conv_wgrad', dev, g.data_ptr(), xs.data_ptr(), ws.data_ptr(), ws.numel(), dwk.data_ptr(), B, co, ci, k, pad, dil, L, 1,
                   float(slope))
             db = _floats(dev, co)
-            _call('dsv_hgt_bias_grad', dev, g.data_ptr(), bws.data_ptr(), bws.numel(), db.data_ptr(), B, co, L)
+            _lib.call('dsv_hgt_bias_grad', dev, g.data_ptr(), bws.data_ptr(), bws.numel(), db.data_ptr(), B, co, L)
             grads[prefix] = (dwk.view(co, k, ci).permute(0, 2, 1).contiguous(), db)
             if not need_dx:
                 return None
             dx = _act(dev, B, ci, L)
             wt = ops.pack(w.flip(2).transpose(0, 1).contiguous())
-            _call('dsv_hgt_conv_dgrad', dev, g.data_ptr(), wt.data_ptr(), xs.data_ptr(), _ptr(residual), _ptr(sum_in), dx.data_ptr(), B, co, ci, k, pad,
+            _lib.call('dsv_hgt_conv_dgrad', dev, g.data_ptr(), wt.data_ptr(), xs.data_ptr(), _lib.ptr(residual), _lib.ptr(sum_in), dx.data_ptr(), B, co, ci, k, pad,
                   dil, L, float(slope), float(divide))
             return dx
 
         L = Lh
         gp = _act(dev, B, 1, L)
-        _call('dsv_hgt_tanh_backward', dev, gy.to(torch.float32).contiguous().data_ptr(), o.data_ptr(), gp.data_ptr(), B, L)
+        _lib.call('dsv_hgt_tanh_backward', dev, gy.to(torch.float32).contiguous().data_ptr(), o.data_ptr(), gp.data_ptr(), B, L)
         G = conv_bwd('conv_post.', gp, pre[-1], wts['conv_post.'], L, 1, POST_SLOPE, divide=float(nk))
         npair = 2 if kind == '1' else 1
         per_rb = [len(tuple(h['resblock_dilation_sizes'][j])[:3 if kind == '1' else 2]) for j in range(nk)]
@@ -270,7 +258,7 @@ class HifiGanGenFunction(torch.autograd.Function):
                 C, K = nwt.shape[0], nwt.shape[2]
                 s = int(np.prod(rates[i + 1:])) if i + 1 < len(rates) else 1
                 dnw, dnb = _floats(dev, C * K), _floats(dev, C)
-                _call('dsv_hgt_noise_conv_backward', dev, Gin.data_ptr(), har.data_ptr(), nwt.reshape(C, K).contiguous().data_ptr(), bws.data_ptr(),
+                _lib.call('dsv_hgt_noise_conv_backward', dev, Gin.data_ptr(), har.data_ptr(), nwt.reshape(C, K).contiguous().data_ptr(), bws.data_ptr(),
                       bws.numel(), dnw.data_ptr(), dnb.data_ptr(), dhar.data_ptr(), B, C, K, s, s // 2 if i + 1 < len(rates) else 0, Lh, L, 1 if first_noise else 0)
                 first_noise = False
                 grads[f'noise_convs.{i}.'] = (dnw.view(C, 1, K), dnb)
@@ -281,21 +269,21 @@ class HifiGanGenFunction(torch.autograd.Function):
             r_of, t_of, kk, ppad = polyphase_taps(k, u)
             dwp = _floats(dev, co * u * kk * ci)
             xup = pre[base]
-            _call('dsv_hgt_conv_wgrad', dev, Gin.data_ptr(), xup.data_ptr(), ws.data_ptr(), ws.numel(), dwp.data_ptr(), B, co, ci, kk, ppad, 1, L_in, u,
+            _lib.call('dsv_hgt_conv_wgrad', dev, Gin.data_ptr(), xup.data_ptr(), ws.data_ptr(), ws.numel(), dwp.data_ptr(), B, co, ci, kk, ppad, 1, L_in, u,
                   LRELU_SLOPE)
             dub = _floats(dev, co)
-            _call('dsv_hgt_bias_grad', dev, Gin.data_ptr(), bws.data_ptr(), bws.numel(), dub.data_ptr(), B, co, L)
+            _lib.call('dsv_hgt_bias_grad', dev, Gin.data_ptr(), bws.data_ptr(), bws.numel(), dub.data_ptr(), B, co, L)
             dwv = dwp.view(co, u, kk, ci)                            # tap j of the plain weight sits at phase r_of[j], column t_of[j] (slices: nothing is copied from the host)
             grads[f'ups.{i}.'] = (torch.stack([dwv[:, r_of[j], t_of[j], :] for j in range(k)], 2).permute(1, 0, 2).contiguous(), dub)
             dx = _act(dev, B, ci, L_in)
-            _call('dsv_hgt_upsample_dgrad', dev, Gin.data_ptr(), uw.data_ptr(), xup.data_ptr(), dx.data_ptr(), B, ci, co, u, k, L_in, LRELU_SLOPE,
+            _lib.call('dsv_hgt_upsample_dgrad', dev, Gin.data_ptr(), uw.data_ptr(), xup.data_ptr(), dx.data_ptr(), B, ci, co, u, k, L_in, LRELU_SLOPE,
                   float(nk) if i > 0 else 1.0)
             G, L = dx, L_in
         conv_bwd('conv_pre.', G, xin, None, T, 1, 1.0, need_dx=False)
         if nsf:
             H = sines.shape[2]
             dlw, dlb = _floats(dev, H), _floats(dev, 1)
-            _call('dsv_hgt_source_backward', dev, dhar.data_ptr(), har.data_ptr(), sines.data_ptr(), dlw.data_ptr(), dlb.data_ptr(), B, Lh, H)
+            _lib.call('dsv_hgt_source_backward', dev, dhar.data_ptr(), har.data_ptr(), sines.data_ptr(), dlw.data_ptr(), dlb.data_ptr(), B, Lh, H)
             grads['m_source.l_linear.'] = (dlw.view(1, H), dlb)
         flat = []
         for n, (p, _) in enumerate(layout):

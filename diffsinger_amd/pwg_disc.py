@@ -38,19 +38,9 @@ def launch_count() -> int:
     return _LAUNCHES[0]
 
 
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _call(name, n, dev, *args):
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
+    _lib.call(name, dev, *args)
     _LAUNCHES[0] += n
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
 
 
 def _pad_rows(x2d: torch.Tensor, T: int) -> torch.Tensor:
@@ -82,12 +72,12 @@ class PwgDiscFunction(torch.autograd.Function):
         w0, wl = ws[0].detach().contiguous(), ws[n - 1].detach().contiguous()
         b = [None if t is None else t.detach().contiguous() for t in bs]
         acts = [torch.empty(B, _C, LS, device=dev, dtype=torch.float32) for _ in range(n - 1)]
-        _call('dsv_pwgd_first', 1, dev, xp.data_ptr(), w0.data_ptr(), _ptr(b[0]), acts[0].data_ptr(), B, T, slope)
+        _call('dsv_pwgd_first', 1, dev, xp.data_ptr(), w0.data_ptr(), _lib.ptr(b[0]), acts[0].data_ptr(), B, T, slope)
         for l in range(1, n - 1):
             off = (l - 1) * 2 * _C * 3 * _C * 4
-            _call('dsv_pwgd_layer', 1, dev, acts[l - 1].data_ptr(), packed.data_ptr() + off, _ptr(b[l]), None, acts[l].data_ptr(), B, T, l, slope, 0)
+            _call('dsv_pwgd_layer', 1, dev, acts[l - 1].data_ptr(), packed.data_ptr() + off, _lib.ptr(b[l]), None, acts[l].data_ptr(), B, T, l, slope, 0)
         p = torch.empty(B, LS, device=dev, dtype=torch.float32)
-        _call('dsv_pwgd_last', 1, dev, acts[n - 2].data_ptr(), wl.data_ptr(), _ptr(b[n - 1]), p.data_ptr(), B, T)
+        _call('dsv_pwgd_last', 1, dev, acts[n - 2].data_ptr(), wl.data_ptr(), _lib.ptr(b[n - 1]), p.data_ptr(), B, T)
         ctx.save_for_backward(xp, packed, w0, wl, *acts)
         ctx.meta = (B, T, float(slope), n, [t is not None for t in bs])
         out = p[:, None, :T]
@@ -115,11 +105,11 @@ class PwgDiscFunction(torch.autograd.Function):
         G = torch.empty(B, _C, LS, device=dev, dtype=torch.float32)
         G2 = torch.empty_like(G)
         _call('dsv_pwgd_last_backward', 3, dev, g.data_ptr(), acts[n - 2].data_ptr(), wl.data_ptr(), ws_e.data_ptr(), dws[n - 1].data_ptr(),
-              _ptr(dbs[n - 1]), G.data_ptr(), B, T, slope)
+              _lib.ptr(dbs[n - 1]), G.data_ptr(), B, T, slope)
         for l in range(n - 2, 0, -1):
             dws[l] = torch.empty(_C, _C, 3, device=dev, dtype=torch.float32)
             dbs[l] = torch.empty(_C, device=dev, dtype=torch.float32) if has_b[l] else None
-            _call('dsv_pwgd_wgrad', 2, dev, G.data_ptr(), acts[l - 1].data_ptr(), ws_w.data_ptr(), dws[l].data_ptr(), _ptr(dbs[l]), B, T, l)
+            _call('dsv_pwgd_wgrad', 2, dev, G.data_ptr(), acts[l - 1].data_ptr(), ws_w.data_ptr(), dws[l].data_ptr(), _lib.ptr(dbs[l]), B, T, l)
             off = ((l - 1) * 2 + 1) * _C * 3 * _C * 4
             _call('dsv_pwgd_layer', 1, dev, G.data_ptr(), packed.data_ptr() + off, None, acts[l - 1].data_ptr(), G2.data_ptr(), B, T, l, slope, 1)
             G, G2 = G2, G
@@ -127,7 +117,7 @@ class PwgDiscFunction(torch.autograd.Function):
         dbs[0] = torch.empty(_C, device=dev, dtype=torch.float32) if has_b[0] else None
         dx = torch.empty(B, LS, device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         _call('dsv_pwgd_first_backward', 3 if dx is not None else 2, dev, G.data_ptr(), xp.data_ptr(), w0.data_ptr(), ws_e.data_ptr(), dws[0].data_ptr(),
-              _ptr(dbs[0]), _ptr(dx), B, T)
+              _lib.ptr(dbs[0]), _lib.ptr(dx), B, T)
         gx = None if dx is None else dx[:, None, :T]
         return (gx, None, None, None) + tuple(dws) + tuple(dbs)
 

@@ -18,7 +18,6 @@ torch.cuda.graph on a single stream.  Every sum runs in a fixed order: two steps
 from __future__ import annotations
 
 import math
-from typing import Optional
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -37,19 +36,9 @@ def launch_count() -> int:
     return _LAUNCHES[0]
 
 
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _call(name, n, dev, *args):
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, name)(*args, _stream(dev)), name)
+    _lib.call(name, dev, *args)
     _LAUNCHES[0] += n
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
 
 
 def _new(dev, *shape):
@@ -78,7 +67,7 @@ def _pack(mat: torch.Tensor) -> torch.Tensor:
 def _conv(x, L, wp, bias, rows, ci, k, pre_slope=1.0):
     """dsv_conv1d without padding or dilation (the inference path's call for conv_in and last_conv_layers)"""
     out = _new(x.device, x.shape[0], rows, padded_samples(L))
-    _call('dsv_conv1d', 1, x.device, x.data_ptr(), wp.data_ptr(), _ptr(bias), out.data_ptr(), x.shape[0], ci, rows, k, 0, 1, L, 1, float(pre_slope),
+    _call('dsv_conv1d', 1, x.device, x.data_ptr(), wp.data_ptr(), _lib.ptr(bias), out.data_ptr(), x.shape[0], ci, rows, k, 0, 1, L, 1, float(pre_slope),
           None, None, 1.0, 0)
     return out
 
@@ -129,8 +118,8 @@ class PwgGenFunction(torch.autograd.Function):
         for i, (blk, dil) in enumerate(zip(blocks, dils)):
             b2 = None if blk[4] is None else torch.cat([blk[4], blk[6]])
             a, xo = _new(dev, B, 128, LS), _new(dev, B, 64, LS)
-            _call('dsv_pwgt_layer', 1, dev, xs[i].data_ptr(), y.data_ptr(), p1.data_ptr() + 4 * i * (n1 // 8) * 256 * 4, _ptr(blk[1]),
-                  p2.data_ptr() + 4 * i * 8 * 256 * 4, _ptr(b2), xo.data_ptr(), skips.data_ptr(), a.data_ptr(), B, T, aux, dil, 1 if i == 0 else 0)
+            _call('dsv_pwgt_layer', 1, dev, xs[i].data_ptr(), y.data_ptr(), p1.data_ptr() + 4 * i * (n1 // 8) * 256 * 4, _lib.ptr(blk[1]),
+                  p2.data_ptr() + 4 * i * 8 * 256 * 4, _lib.ptr(b2), xo.data_ptr(), skips.data_ptr(), a.data_ptr(), B, T, aux, dil, 1 if i == 0 else 0)
             acts.append(a)
             xs.append(xo)
         S = skips * math.sqrt(1.0 / nl)
@@ -187,12 +176,12 @@ class PwgGenFunction(torch.autograd.Function):
         grads = []
         for i in range(nl - 1, -1, -1):
             a = acts[i]
-            _call('dsv_pwgt_gate_backward', 1, dev, _ptr(dxp), dS.data_ptr(), a.data_ptr(), w2t.data_ptr() + 2 * i * 16 * 256 * 4, da.data_ptr(), B, T)
+            _call('dsv_pwgt_gate_backward', 1, dev, _lib.ptr(dxp), dS.data_ptr(), a.data_ptr(), w2t.data_ptr() + 2 * i * 16 * 256 * 4, da.data_ptr(), B, T)
             o2, o1g = _new(dev, 128 * 64 + 128), _new(dev, 128 * n1 + 128)
-            _call('dsv_pwgt_wgrad_out', 2, dev, _ptr(dxp), dS.data_ptr(), a.data_ptr(), ws.data_ptr(), o2.data_ptr(), B, T)
+            _call('dsv_pwgt_wgrad_out', 2, dev, _lib.ptr(dxp), dS.data_ptr(), a.data_ptr(), ws.data_ptr(), o2.data_ptr(), B, T)
             _call('dsv_pwgt_wgrad_conv', 2, dev, da.data_ptr(), xs[i].data_ptr(), y.data_ptr(), ws.data_ptr(), o1g.data_ptr(), B, T, aux, dils[i])
             dxn = dxb[i & 1]
-            _call('dsv_pwgt_conv_backward', 1, dev, da.data_ptr(), _ptr(dxp), w1t.data_ptr() + 2 * i * 48 * 256 * 4,
+            _call('dsv_pwgt_conv_backward', 1, dev, da.data_ptr(), _lib.ptr(dxp), w1t.data_ptr() + 2 * i * 48 * 256 * 4,
                   wat.data_ptr() + (R // 32) * i * 16 * 256 * 4, dxn.data_ptr(), dC.data_ptr(), B, T, aux, dils[i], 1 if i == nl - 1 else 0)
             m1 = o1g[:128 * n1].reshape(128, n1)
             m2 = o2[:128 * 64].reshape(128, 64)

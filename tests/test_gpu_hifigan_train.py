@@ -126,6 +126,24 @@ def test_conv_backward(ops, B, C, K, dil, L, form):
     check('db', ops.bias(g, B, Co, L), wb, bb)
 
 
+@pytest.mark.parametrize('L', [1, 31, 513, 1061])
+def test_both_weight_gradients_return_the_same_bits_where_they_state_the_same_sum(ops, L):
+    """dsv_pwgt_wgrad_relu (rows 0..63 of its [128][64] block) and dsv_hgt_conv_wgrad at Co = Ci = 64, K = 1, slope 0 state the same sum
+    sum_t g[co][t] relu(saved[ci][t]) on the same 512-sample splits, the same tile step and the same float64 reduction (the two kernels are
+    one pattern written twice; this is the guard for folding them into one): equal bits.  (The leaky ReLU with slope 0 stages -0 where the
+    ReLU stages +0; the accumulators start at +0, so no result bit sees it.)  L: one partial step, one short of a step, the split + 1, two
+    splits + 37."""
+    B = 2
+    g, saved = ops.padded(rnd(B, 64, L, seed=7 * L + 1)), ops.padded(rnd(B, 64, L, seed=7 * L + 2))
+    assert 0.3 < float((saved[..., :L] < 0).float().mean()) < 0.7
+    ws = torch.full((ops.lib.dsv_pwgt_wgrad_workspace_floats(B, L, 64),), NAN, device=DEV)
+    out = ops.nan(128 * 64 + 128)
+    ops.call('dsv_pwgt_wgrad_relu', g.data_ptr(), saved.data_ptr(), ws.data_ptr(), out.data_ptr(), B, L)
+    dw = ops.wgrad(g, saved, B, 64, 64, 1, 0, 1, L, 1, 0.0).reshape(64, 64)
+    assert bool(torch.isfinite(dw).all()) and float(dw.abs().max()) > 0
+    assert torch.equal(out[:64 * 64].reshape(64, 64), dw)
+
+
 # ---- 2. transposed convolution ------------------------------------------------------------------------------------------------------------------
 def taps_of(k, u):
     """out[u q + r] takes tap j from input sample q + (r + p - j) / u, r = (j - p) mod u: per tap its phase and its column in the polyphase filter"""
