@@ -10,8 +10,8 @@
 //   k_pe_bn_train_bwd    dgamma, dbeta and dx = gamma rstd (g - mean(g) - xhat mean(g xhat)), g = dy * keep, times (pre > 0) under relu_in;
 //                        one workgroup per channel, two passes.
 //   k_pe_gn_bwd          backward of k_fs_group_norm (GroupNorm + ReLU; the residual's gradient is dy itself): one workgroup per (group,
-//                        utterance) recomputes mean / rstd with the forward's own loops (so the ReLU mask is the forward's, bit for bit), each
-//                        wave sums the channels it owns (dgamma / dbeta partials of this utterance -> workspace), then dx.
+//                        utterance) recomputes the mean (pivot + dm) / rstd with the forward's own loops (so the ReLU mask is the forward's, bit
+//                        for bit), each wave sums the channels it owns (dgamma / dbeta partials of this utterance -> workspace), then dx.
 //   k_pe_gn_reduce       dgamma[c] / dbeta[c] = the utterances' partials added in utterance order.
 //   k_pe_f0_partial / k_pe_f0_final / k_pe_f0_bwd    FastSpeech2Task.add_f0_loss (tasks/tts/fs2.py:254-269) with the caller's nonpadding mask:
 //                        uv = sum(BCEWithLogits(p1, uv) np) / sum(np) lambda_uv, f0 = sum(|p0 - f0| np') / sum(np') lambda_f0 (l2: the square),
@@ -176,12 +176,13 @@ __global__ __launch_bounds__(256) void k_pe_gn_bwd(const float* __restrict__ x, 
     const int cg = C / G;
     const size_t base = ((size_t)bb * C + (size_t)g * cg) * TS;
     const int n = cg * T;
-    // mean / rstd: the loops of k_fs_group_norm, so that the ReLU mask below is the forward's
+    // pivot + dm / rstd: the loops of k_fs_group_norm, so that the ReLU mask below is the forward's
+    const float pivot = x[base];
     float s = 0.f;
-    for (int i = tid; i < n; i += 256) { const int c = i / T, t = i - c * T; s += x[base + (size_t)c * TS + t]; }
-    const float mean = fs_block_sum(s, red) / (float)n;
+    for (int i = tid; i < n; i += 256) { const int c = i / T, t = i - c * T; s += x[base + (size_t)c * TS + t] - pivot; }
+    const float dm = fs_block_sum(s, red) / (float)n;
     float d = 0.f;
-    for (int i = tid; i < n; i += 256) { const int c = i / T, t = i - c * T; const float e = x[base + (size_t)c * TS + t] - mean; d += e * e; }
+    for (int i = tid; i < n; i += 256) { const int c = i / T, t = i - c * T; const float e = (x[base + (size_t)c * TS + t] - pivot) - dm; d += e * e; }
     const float var = fs_block_sum(d, red) / (float)n;
     const float rstd = 1.f / sqrtf(var + eps);
     // wave w owns channels w, w + 4, ...: sum over the frames of gz = dy * (z > 0) and of gz * xhat
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(256) void k_pe_gn_bwd(const float* __restrict__ x, 
         float a = 0.f, b = 0.f;
         for (int t = lane; t < T; t += 64) {
             const size_t o = base + (size_t)c * TS + t;
-            const float xh = (x[o] - mean) * rstd;
+            const float xh = ((x[o] - pivot) - dm) * rstd;
             float gz = dy[o];
             if (relu && !(xh * ga + be > 0.f)) gz = 0.f;
             a += gz * xh;
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(256) void k_pe_gn_bwd(const float* __restrict__ x, 
         if (t < T) {
             const int ch = g * cg + c;
             const float ga = gamma[ch];
-            const float xh = (x[o] - mean) * rstd;
+            const float xh = ((x[o] - pivot) - dm) * rstd;
             float gz = dy[o];
             if (relu && !(xh * ga + beta[ch] > 0.f)) gz = 0.f;
             v = rstd * (gz * ga - m1 - xh * m2);

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from diffsinger_amd import hparams
 from oracle import pe_oracle as PO
+from tests import pe_edge_helpers as E
 from tests import pe_train_helpers as PH
 
 pytestmark = pytest.mark.gpu
@@ -23,10 +24,7 @@ WIDE = dict(PH.HP, hidden_size=256)                 # the shipped width: GroupNo
 WIDE_CASE = dict(B=2, T=40, seed=506)           # the first seed from 501 that meets the 8x ReLU condition on the CPU
 
 
-def _check(name, got, x64, ref32):
-    err, ref = PH.rel_err(got, x64), PH.rel_err(ref32, x64)
-    print(f'{name}: err {err:.3e}  fp32 reference {ref:.3e}  bound {PH.bound(ref):.3e}')
-    assert err <= PH.bound(ref), (name, err, ref)
+_check = E.check                                    # shared with tests/test_gpu_pe_edges.py
 
 
 def _check_dev(name, got, x64, dev):
@@ -38,17 +36,7 @@ def _check_dev(name, got, x64, dev):
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. BatchNorm on batch statistics
 # ---------------------------------------------------------------------------------------------------------------------
-def _bn_reference(x, gamma, beta, rm, rv, keep, dy, relu_in, dtype):
-    """y = native_batch_norm(relu(x)) * keep and its gradients under L = sum(y dy), on [B,C,T] tensors in `dtype`."""
-    x = x.to(dtype).clone().requires_grad_(True)
-    gamma, beta = gamma.to(dtype).clone().requires_grad_(True), beta.to(dtype).clone().requires_grad_(True)
-    rm, rv = rm.to(dtype).clone(), rv.to(dtype).clone()
-    r = F.relu(x) if relu_in else x
-    y, mean, rstd = torch.native_batch_norm(r, gamma, beta, rm, rv, True, 0.1, 1e-5)
-    y = y * keep.to(dtype)[:, None, :]
-    (y * dy.to(dtype)).sum().backward()
-    return {'y': y.detach(), 'save_mean': mean.detach(), 'save_rstd': rstd.detach(), 'running_mean': rm, 'running_var': rv, 'dx': x.grad,
-            'dgamma': gamma.grad, 'dbeta': beta.grad}
+_bn_reference = E.bn_reference                      # y = native_batch_norm(relu(x)) * keep and its gradients under L = sum(y dy)
 
 
 @pytest.mark.parametrize('B,T,kind', [(3, 75, 'kink_free'), (1, 2, 'kink_free'), (3, 75, 'cancellation')])
@@ -110,11 +98,7 @@ def _gn_case(B, C, G, T):
     raise AssertionError('no seed keeps the pre-ReLU values away from zero')
 
 
-def _gn_reference(x, gamma, beta, res, dy, G, dtype):
-    x, gamma, beta, res = (t.to(dtype).clone().requires_grad_(True) for t in (x, gamma, beta, res))
-    y = res + F.relu(F.group_norm(x, G, gamma, beta, 1e-5))
-    (y * dy.to(dtype)).sum().backward()
-    return {'y': y.detach(), 'dx': x.grad, 'dgamma': gamma.grad, 'dbeta': beta.grad, 'dres': res.grad}
+_gn_reference = E.gn_reference                      # y = res + relu(group_norm(x)) and its gradients under L = sum(y dy)
 
 
 @pytest.mark.parametrize('B,C,G,T', [(3, 64, 4, 75), (2, 256, 16, 40)])
