@@ -16,6 +16,9 @@ Public surface mirrors the reference's own plugin API for this path:
     pwg_generator_losses, pwg_discriminator_losses, pwg_training_step
                                         the ParallelWaveGAN trainer's two objectives and one step of it (configs/tts/pwg.yaml) on
                                         ParallelWaveGANGenerator.forward_train (diffsinger_amd/pwg_train.py, + pwg_gen_op)
+    avg_pool_op, cond_discriminator_loss
+                                        MultiScaleDiscriminator's AvgPool1d(4, 2, 1) on HIP, forward and backward (modules/hifigan/hifigan.py:304)
+                                        and hifigan.py:350-356 (diffsinger_amd/hifigan_disc.py)
     pe_losses(output, sample, hp), pe_training_step(model, sample, hp)
                                         PitchExtractionTask.run_model / ._training_step (tasks/tts/pe.py:111-155) on the HIP PitchExtractor
                                         (diffsinger_amd/pe.py)
@@ -28,6 +31,7 @@ __all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiff
            'STFTLoss', 'MultiResolutionSTFTLoss', 'stft_adjoint_op', 'spectral_loss_op',
            'ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss',
            'pwg_gen_op', 'pwg_generator_losses', 'pwg_discriminator_losses', 'pwg_training_step',
+           'avg_pool_op', 'cond_discriminator_loss',
            'pe_losses', 'pe_training_step']
 
 
@@ -50,6 +54,9 @@ def __getattr__(name):      # lazy: torch-heavy modules load on first use
     if name in ('pwg_gen_op', 'pwg_generator_losses', 'pwg_discriminator_losses', 'pwg_training_step'):
         from . import pwg_train
         return getattr(pwg_train, name)
+    if name in ('avg_pool_op', 'cond_discriminator_loss'):
+        from . import hifigan_disc
+        return getattr(hifigan_disc, name)
     if name in ('pe_losses', 'pe_training_step'):
         from . import pe
         return getattr(pe, name)

@@ -48,7 +48,8 @@ SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'ds
                'dsv_pwgt_conv_backward', 'dsv_pwgt_wgrad_conv', 'dsv_pwgt_wgrad_out', 'dsv_pwgt_wgrad_relu', 'dsv_pwgt_rowdot', 'dsv_pwgt_last_dgrad',
                'dsv_pwgt_relu_mask', 'dsv_pwgt_upsample_backward', 'dsv_pwgt_convin_wgrad',
                'dsv_hgt_wgrad_split', 'dsv_hgt_act_floats', 'dsv_hgt_wgrad_workspace_floats', 'dsv_hgt_conv_dgrad', 'dsv_hgt_conv_wgrad', 'dsv_hgt_bias_workspace_floats', 'dsv_hgt_bias_grad',
-               'dsv_hgt_upsample_dgrad', 'dsv_hgt_tanh_backward', 'dsv_hgt_noise_conv_backward', 'dsv_hgt_source_mix', 'dsv_hgt_source_backward']
+               'dsv_hgt_upsample_dgrad', 'dsv_hgt_tanh_backward', 'dsv_hgt_noise_conv_backward', 'dsv_hgt_source_mix', 'dsv_hgt_source_backward',
+               'dsv_hgd_pool_samples', 'dsv_hgd_avgpool', 'dsv_hgd_avgpool_backward']
 
 _fp = C.POINTER(C.c_float)
 _fpp = C.POINTER(C.c_void_p)
@@ -300,6 +301,10 @@ def load():
     lib.dsv_hgt_noise_conv_backward.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.dsv_hgt_source_mix.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, f32, vp]
     lib.dsv_hgt_source_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.dsv_hgd_pool_samples.argtypes = [i32]
+    lib.dsv_hgd_pool_samples.restype = i32
+    lib.dsv_hgd_avgpool.argtypes = [vp, vp, i64, i32, i64, vp]
+    lib.dsv_hgd_avgpool_backward.argtypes = [vp, vp, i64, i32, i64, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('dsd_abi_version',):

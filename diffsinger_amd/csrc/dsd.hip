@@ -1446,4 +1446,5 @@ extern "C" int dsd_debug_layer_timeline(dsd_handle* h, int32_t layer, int32_t t,
 #include "pwg_disc_abi.hpp"
 #include "pwg_train_abi.hpp"
 #include "hifigan_train_abi.hpp"
+#include "hifigan_disc.hpp"
 #include "pe_train.hpp"

@@ -19,3 +19,16 @@ static int voc_check_f64_workspace(const char* who, const void* ptr, const char*
 
 // splits of `len` samples that cover L
 static int voc_splits(int L, int len) { return (L + len - 1) / len; }
+
+// R rows pooled by AvgPool1d(4, 2, 1) from L samples: `in` holds R rows `ld` floats apart of which `in_len` are read, `out` R rows of `out_ld`
+// floats; the two ranges must not overlap
+static int voc_check_pool_rows(const char* who, const float* in, const float* out, int64_t R, int L, int64_t ld, int in_len, int out_ld) {
+    if (!in || !out) return fail(DSD_ERR_INVALID, "%s: null argument", who);
+    if (R < 1 || R > 65535 || L < 2 || L > (1 << 30) || ld < in_len || ld > ((int64_t)1 << 31))
+        return fail(DSD_ERR_INVALID, "%s: bad shape (R=%lld in [1, 65535], L=%d in [2, 2^30], row stride %lld in [%d, 2^31])", who, (long long)R, L,
+                    (long long)ld, in_len);
+    const float* in_end = in + (R - 1) * ld + in_len;
+    const float* out_end = out + R * (int64_t)out_ld;
+    if (in < out_end && out < in_end) return fail(DSD_ERR_INVALID, "%s: input and output overlap", who);
+    return DSD_OK;
+}

@@ -418,6 +418,18 @@ int dsv_hgt_source_mix(const float* f0, const float* sines_ws, const float* nois
 int dsv_hgt_source_backward(const float* dhar, const float* har, const float* sines, float* dw, float* db, int32_t B, int32_t L, int32_t H,
                             void* stream);
 
+/* HiFi-GAN scale discriminator: the pooling of MultiScaleDiscriminator (modules/hifigan/hifigan.py:304-307, :316-317), forward and backward -
+ * csrc/hifigan_disc.hpp.  Conventions of the section above: output rows [R][LS(L)]; every call leaves [L, LS) of its outputs at zero; no atomics, a
+ * fixed order of additions (two calls are bitwise equal); nothing allocates, synchronises or reads a device value on the host; everything is
+ * enqueued on `stream`; bad shapes are refused with DSD_ERR_INVALID before any launch.
+ * dsv_hgd_avgpool / _backward: AvgPool1d(4, 2, padding = 1), divisor always 4 (count_include_pad), over R rows: x, rows ld_x >= L floats apart (a
+ *   dense [R][L] tensor: ld_x = L; nothing is read beyond sample L of a row) -> out [R][LS(L / 2)], L >= 2, R <= 65535 (dsv_hgd_pool_samples(L) =
+ *   L / 2, -1 for L < 2); the backward takes g, rows ld_g >= L / 2 floats apart, and writes dx [R][LS(L)], L the FORWARD's input length.  Input
+ *   and output must not overlap. */
+int32_t dsv_hgd_pool_samples(int32_t L);
+int dsv_hgd_avgpool(const float* x, float* out, int64_t R, int32_t L, int64_t ld_x, void* stream);
+int dsv_hgd_avgpool_backward(const float* g, float* dx, int64_t R, int32_t L, int64_t ld_g, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
