@@ -191,8 +191,11 @@ int dsv_pwg_layer(const float* x, const float* c, const float* w1_packed, const 
  * 'constant'), data_gen/tts/data_gen_utils.py:123-124; DSV_STFT_PAD_REFLECT: torch's 'reflect', modules/hifigan/mel_utils.py:66-71, pads < L);
  * "center" is pad_l = pad_r = n_fft / 2.  n_frames = dsv_stft_frames(L, ...) = 1 + (L + pad_l + pad_r - n_fft) / hop (-1: not one frame).
  * `lengths` (device int32 [B], or NULL): valid samples per row; a row then has 1 + (len + pad_l + pad_r - n_fft) / hop valid frames (0 when
- * that is not one frame; padding reflects about the row's own end), written to frames_out [B] (device, or NULL).  FRAMES AT OR BEYOND A ROW'S
- * VALID COUNT ARE WRITTEN AS EXACTLY 0 by dsv_stft and dsv_logmel - the library's padding value for mels. */
+ * that is not one frame; padding reflects about the row's own end), written to frames_out [B] (device, or NULL).  A length outside [0, L] is
+ * clamped to it.  The reflect-padding condition pads < L is checked against L, not against lengths[b]: a row NO LONGER THAN ITS PADDING is
+ * padded by a SINGLE reflection about its own first / last sample, and by 0 where that reflection leaves the row (torch refuses such a row;
+ * a row of one sample is that sample between zeros).  FRAMES AT OR BEYOND A ROW'S VALID COUNT ARE WRITTEN AS EXACTLY 0 by dsv_stft and
+ * dsv_logmel - the library's padding value for mels. */
 #define DSV_STFT_BASIS_FWD 0
 #define DSV_STFT_BASIS_INV 1
 #define DSV_STFT_PAD_CONSTANT 0
