@@ -19,6 +19,12 @@ Public surface mirrors the reference's own plugin API for this path:
     avg_pool_op, cond_discriminator_loss
                                         MultiScaleDiscriminator's AvgPool1d(4, 2, 1) on HIP, forward and backward (modules/hifigan/hifigan.py:304)
                                         and hifigan.py:350-356 (diffsinger_amd/hifigan_disc.py)
+    HifiGanMelLoss, mel_spectrogram_loss_op, spec_logmel_op
+                                        the mel-spectrogram loss of the HiFi-GAN trainer (modules/hifigan/mel_utils.py:45-76, lambda_mel) on
+                                        the differentiable log-mel (diffsinger_amd/mel_loss.py, diffsinger_amd/stft.py)
+    hifigan_generator_losses, hifigan_generator_step
+                                        the mel term of the HiFi-GAN generator objective and one step on it, on
+                                        HifiGanGenerator.forward_train (diffsinger_amd/hifigan_train.py); no adversarial term yet
     pe_losses(output, sample, hp), pe_training_step(model, sample, hp)
                                         PitchExtractionTask.run_model / ._training_step (tasks/tts/pe.py:111-155) on the HIP PitchExtractor
                                         (diffsinger_amd/pe.py)
@@ -32,7 +38,8 @@ __all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiff
            'ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss',
            'pwg_gen_op', 'pwg_generator_losses', 'pwg_discriminator_losses', 'pwg_training_step',
            'avg_pool_op', 'cond_discriminator_loss',
-           'pe_losses', 'pe_training_step']
+           'pe_losses', 'pe_training_step',
+           'HifiGanMelLoss', 'mel_spectrogram_loss_op', 'spec_logmel_op', 'hifigan_generator_losses', 'hifigan_generator_step']
 
 
 def __getattr__(name):      # lazy: torch-heavy modules load on first use
@@ -60,4 +67,13 @@ def __getattr__(name):      # lazy: torch-heavy modules load on first use
     if name in ('pe_losses', 'pe_training_step'):
         from . import pe
         return getattr(pe, name)
+    if name in ('HifiGanMelLoss', 'mel_spectrogram_loss_op'):
+        from . import mel_loss
+        return getattr(mel_loss, name)
+    if name == 'spec_logmel_op':
+        from .stft import spec_logmel_op
+        return spec_logmel_op
+    if name in ('hifigan_generator_losses', 'hifigan_generator_step'):
+        from . import hifigan_train
+        return getattr(hifigan_train, name)
     raise AttributeError(name)

@@ -41,6 +41,7 @@ SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'ds
                'dsv_logmel',
                'dsv_stft_make_adjoint_basis', 'dsv_stft_adjoint_workspace_floats', 'dsv_stft_adjoint', 'dsv_spectral_loss_workspace_floats', 'dsv_spectral_loss',
                'dsv_spectral_loss_backward',
+               'dsv_mel_spectrum', 'dsv_mel_head', 'dsv_mel_head_backward', 'dsv_mel_clamp_backward',
                'dsv_pwgd_tile', 'dsv_pwgd_wgrad_split', 'dsv_pwgd_wgrad_workspace_floats', 'dsv_pwgd_edge_workspace_floats', 'dsv_pwgd_layer', 'dsv_pwgd_wgrad',
                'dsv_pwgd_first', 'dsv_pwgd_first_backward', 'dsv_pwgd_last', 'dsv_pwgd_last_backward', 'dsv_pwgd_lsgan_workspace_floats', 'dsv_pwgd_lsgan',
                'dsv_pwgd_lsgan_backward',
@@ -250,6 +251,10 @@ def load():
     lib.dsv_spectral_loss_workspace_floats.restype = i64
     lib.dsv_spectral_loss.argtypes = [vp, vp, vp, vp, i64, vp]
     lib.dsv_spectral_loss_backward.argtypes = [vp, vp, vp, vp, vp, i64, vp]
+    lib.dsv_mel_spectrum.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.dsv_mel_head.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, vp]
+    lib.dsv_mel_head_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, vp]
+    lib.dsv_mel_clamp_backward.argtypes = [vp, vp, vp, i64, vp]
     lib.dsv_pwgd_tile.argtypes = []
     lib.dsv_pwgd_tile.restype = i32
     lib.dsv_pwgd_wgrad_split.argtypes = []

@@ -1443,6 +1443,7 @@ extern "C" int dsd_debug_layer_timeline(dsd_handle* h, int32_t layer, int32_t t,
 #include "fs2_regulate.hpp"
 #include "voc_stft_abi.hpp"
 #include "voc_stft_loss_abi.hpp"
+#include "voc_mel_abi.hpp"
 #include "pwg_disc_abi.hpp"
 #include "pwg_train_abi.hpp"
 #include "hifigan_train_abi.hpp"

@@ -3,6 +3,9 @@ csrc/hifigan_train.hpp).
 
     hifigan_gen_op      the generator on plain weights, forward and backward through ONE autograd node (HifiGanGenFunction);
                         HifiGanGenerator.forward_train applies the weight-norm expression in torch and calls it
+    hifigan_generator_losses, hifigan_generator_step
+                        the mel term of the generator objective (lambda_mel * HifiGanMelLoss, diffsinger_amd/mel_loss.py) and one step on it;
+                        the adversarial and feature-matching terms are not built
 
 The forward is the inference path's one-launch-per-convolution form (dsv_conv1d / dsv_conv1d_folded, bit-identical to the fused chains, DESIGN.md
 section 6): every convolution's input is a tensor in memory and the leaky ReLU in front of it is applied while the kernel stages it, so the saved
@@ -22,7 +25,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from .vocoder import LRELU_SLOPE, MAX_REACH, _HipOps, fold_weight, get_padding, padded_samples, polyphase_weight
 
-__all__ = ['hifigan_gen_op', 'param_layout']
+__all__ = ['hifigan_gen_op', 'param_layout', 'hifigan_generator_losses', 'hifigan_generator_step']
 
 POST_SLOPE = 0.01                  # F.leaky_relu's default slope in front of conv_post (hifigan.py:167)
 SINE_AMP, NOISE_STD, VOICED_THRESHOLD = 0.1, 0.003, 0.0
@@ -301,3 +304,33 @@ def hifigan_gen_op(x, f0, rand_ini, noise, h, params, *, return_saved=False):
     if f0 is None:
         return out[0], list(out[1:]), None
     return out[0], list(out[1:-1]), out[-1]
+
+
+def hifigan_generator_losses(gen, mel_loss, x, f0, y, *, lambda_mel, rand_ini=None, noise=None):
+    """The mel term of the HiFi-GAN generator objective (configs/tts/hifigan.yaml lambda_mel): y_hat = gen.forward_train(x, f0) on the given
+    source draws, mel = mel_loss(y_hat, y) (diffsinger_amd.mel_loss.HifiGanMelLoss; y the recording [B][1][L] or [B][L]), total = lambda_mel * mel.
+    The adversarial and the feature-matching terms of the reference's generator objective are NOT part of it: the discriminators are not
+    trained on this path yet.  -> (dict(mel, total), y_hat)"""
+    y_hat = gen.forward_train(x, f0, rand_ini=rand_ini, noise=noise)
+    mel = mel_loss(y_hat, y)
+    return {'mel': mel, 'total': lambda_mel * mel}, y_hat
+
+
+def hifigan_generator_step(gen, mel_loss, batch, hp, opt_g=None):
+    """One generator step on the mel term alone, in the shape of pwg_training_step.  batch = dict(x mel [B][80][T], y recording [B][1][T * hop],
+    optionally f0 [B][T], rand_ini, noise - the source draws); hp holds lambda_mel and, optionally, generator_grad_norm.  The gradients are zeroed
+    here (set_to_none), the objective runs backward, the gradients are clipped ONLY when hp carries generator_grad_norm, opt_g.step() when
+    given.  The adversarial and the feature-matching terms are not part of it (see hifigan_generator_losses).
+    -> dict(gen_mel, gen_total, gen_grad_norm): the loss terms and the gradient norm before clipping."""
+    gparams = [p for p in gen.parameters() if p.requires_grad]
+    for p in gparams:
+        p.grad = None
+    losses, _ = hifigan_generator_losses(gen, mel_loss, batch['x'], batch.get('f0'), batch['y'], lambda_mel=hp['lambda_mel'],
+                                         rand_ini=batch.get('rand_ini'), noise=batch.get('noise'))
+    losses['total'].backward()
+    out = {'gen_' + k: v.detach() for k, v in losses.items()}
+    clip = hp.get('generator_grad_norm')
+    out['gen_grad_norm'] = torch.nn.utils.clip_grad_norm_(gparams, float('inf') if clip is None else clip)
+    if opt_g is not None:
+        opt_g.step()
+    return out

@@ -4,7 +4,9 @@ reference's vocoder interface built on them (vocoders/base_vocoder.py:22-39; voc
 
     stft_op / istft_op       librosa.stft / librosa.istft, torch.stft / torch.istft
     denoise_op               vocoders/vocoder_utils.py:7-15 (the post-filter of HifiGAN.spec2wav), waveform in, waveform out, on the device
-    logmel_op                data_gen_utils.py:122-134 ('pwg') and modules/hifigan/mel_utils.py:59-76 ('hifigan')
+    logmel_op                data_gen_utils.py:122-134 ('pwg') and modules/hifigan/mel_utils.py:59-76 ('hifigan'); differentiable with respect
+                             to the waveform (include/dsv.h, section "Mel loss"; kernels: csrc/voc_mel.hpp)
+    spec_logmel_op           the head of that analysis on a given spectrum (magnitude, mel product, log), differentiable with respect to it
     mel_filterbank           librosa.filters.mel (Slaney scale and normalisation), restated: see its docstring
     wav2spec, wav2spec_batch PWG.wav2spec / HifiGAN.wav2spec (static methods of the vocoder classes)
 
@@ -222,7 +224,11 @@ def logmel_op(wav_dev, mel_basis, *, n_fft, hop, win_length=None, flavour='pwg',
     [M][n_fft / 2 + 1], M <= 128 - data of the caller (librosa.filters.mel(...) or mel_filterbank).
     flavour 'pwg': centred, zero padding n_fft / 2, log10(max(mel, eps));  'hifigan': input clamped to [-1, 1], reflect padding
     (n_fft - hop) / 2, sqrt(. + 1e-9), ln(max(mel, 1e-5)).  Any of center, pad_mode, pad, clamp, mag_eps, floor, log10 may be overridden.
-    return_linear: also the magnitude [B][n_frames][n_bins]; return_frames: also the rows' valid frame counts."""
+    return_linear: also the magnitude [B][n_frames][n_bins]; return_frames: also the rows' valid frame counts.
+    A waveform that requires grad makes the call differentiable (one autograd node): dsv_mel_spectrum -> dsv_mel_head forward, and backward
+    dsv_mel_head_backward -> dsv_stft_adjoint with the same padding -> dsv_mel_clamp_backward (flavours that clamp only); the gradient is exactly
+    0 at floored cells and behind clamped samples.  lengths=, return_linear= and return_frames= have no gradient (NotImplementedError).  Without
+    a gradient the call is the single fused launch."""
     if flavour not in _FLAVOURS:
         raise ValueError(f'flavour={flavour!r}: one of {sorted(_FLAVOURS)}')
     win_length = n_fft if win_length is None else win_length
@@ -244,6 +250,13 @@ def logmel_op(wav_dev, mel_basis, *, n_fft, hop, win_length=None, flavour='pwg',
         raise ValueError(f'M={M} mel bins: at most {MAX_MEL_BINS} are supported')
     if not (o['floor'] > 0 and o['mag_eps'] >= 0):
         raise ValueError(f"floor={o['floor']} must be > 0 and mag_eps={o['mag_eps']} >= 0")
+    grad = isinstance(wav_dev, torch.Tensor) and wav_dev.requires_grad and torch.is_grad_enabled()
+    if grad:                                              # before a device is asked for: these hold on a host without one
+        if lengths is not None or return_linear or return_frames:
+            raise NotImplementedError('logmel_op: lengths=, return_linear= and return_frames= have no gradient (detach the waveform, or call it '
+                                      'without them)')
+        if mel_basis.requires_grad:
+            raise NotImplementedError('logmel_op: no gradient with respect to the mel basis (detach it)')
     x = _rows(wav_dev, 'logmel_op')
     B, L = x.shape
     pl, pr = _pads(n_fft, o['center'], o.get('pad'))
@@ -252,7 +265,10 @@ def logmel_op(wav_dev, mel_basis, *, n_fft, hop, win_length=None, flavour='pwg',
     T = n_frames(L, n_fft, hop, pl, pr)
     if not mel_basis.is_cuda:
         raise RuntimeError('logmel_op: mel_basis must be a device tensor (there is no CPU path)')
-    mb = mel_basis.to(device=x.device, dtype=torch.float32).contiguous()
+    mb = mel_basis.detach().to(device=x.device, dtype=torch.float32).contiguous()
+    if grad:
+        return LogmelFunction.apply(x, mb, n_fft, hop, win_length, pl, pr, o['pad_mode'], bool(o['clamp']), float(o['mag_eps']), float(o['floor']),
+                                    bool(o['log10']))
     lens = _lengths(lengths, B, x.device)
     fwd, _ = bases(x.device, n_fft, win_length)
     out = torch.empty(B, T, M, device=x.device, dtype=torch.float32)
@@ -266,6 +282,127 @@ def logmel_op(wav_dev, mel_basis, *, n_fft, hop, win_length=None, flavour='pwg',
                                   1 if o['log10'] else 0, _stream(x.device)), 'dsv_logmel')
     res = (out,) + ((lin,) if return_linear else ()) + ((fc,) if return_frames else ())
     return res[0] if len(res) == 1 else res
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the differentiable chain (include/dsv.h, section "Mel loss"; kernels: csrc/voc_mel.hpp)
+# ------------------------------------------------------------------------------------------------------------------------------------
+def _spectrum_launch(x, n_fft, hop, win_length, pl, pr, pad_mode, clamp):
+    """dsv_mel_spectrum on validated arguments: dsv_stft's launch reading clip(x, -1, 1) when `clamp` -> float32 [B][n_bins][n_frames][2]"""
+    B, L = x.shape
+    T = n_frames(L, n_fft, hop, pl, pr)
+    fwd, _ = bases(x.device, n_fft, win_length)
+    spec = torch.empty(B, n_fft // 2 + 1, T, 2, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dsv_mel_spectrum(x.data_ptr(), fwd.data_ptr(), spec.data_ptr(), B, L, n_fft, hop, pl, pr, _PAD_MODES[pad_mode],
+                                                1 if clamp else 0, _stream(x.device)), 'dsv_mel_spectrum')
+    return spec
+
+
+def _head_launch(S, mb, mag_eps, floor, log10):
+    """dsv_mel_head on validated arguments: S float32 [B][n_bins][T][2], mb float32 [M][n_bins], both contiguous -> (log-mel, linear mel) [B][T][M]"""
+    B, n_bins, T, _ = S.shape
+    M = mb.shape[0]
+    out = torch.empty(B, T, M, device=S.device, dtype=torch.float32)
+    mel = torch.empty(B, T, M, device=S.device, dtype=torch.float32)
+    with torch.cuda.device(S.device):
+        _lib.check(_lib.load().dsv_mel_head(S.data_ptr(), mb.data_ptr(), out.data_ptr(), mel.data_ptr(), B, T, 2 * (n_bins - 1), M, mag_eps, floor,
+                                            1 if log10 else 0, _stream(S.device)), 'dsv_mel_head')
+    return out, mel
+
+
+def _head_backward_launch(S, mb, g, mel, mag_eps, floor, log10):
+    """dsv_mel_head_backward: the cotangent g [B][T][M] of the log-mel -> G [B][n_bins][T][2]"""
+    B, n_bins, T, _ = S.shape
+    G = torch.empty_like(S)
+    with torch.cuda.device(S.device):
+        _lib.check(_lib.load().dsv_mel_head_backward(S.data_ptr(), mb.data_ptr(), g.data_ptr(), mel.data_ptr(), G.data_ptr(), B, T, 2 * (n_bins - 1),
+                                                     mb.shape[0], mag_eps, floor, 1 if log10 else 0, _stream(S.device)), 'dsv_mel_head_backward')
+    return G
+
+
+class MelHeadFunction(torch.autograd.Function):
+    """spec_logmel_op: one launch each way.  S float32 [B][n_bins][T][2] contiguous -> (log-mel, linear mel); the linear mel is saved for the
+    backward and carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, S, mb, mag_eps, floor, log10):
+        out, mel = _head_launch(S, mb, mag_eps, floor, log10)
+        ctx.save_for_backward(S, mb, mel)
+        ctx.consts = (mag_eps, floor, log10)
+        ctx.mark_non_differentiable(mel)
+        return out, mel
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_mel):
+        S, mb, mel = ctx.saved_tensors
+        return _head_backward_launch(S, mb, g.to(torch.float32).contiguous(), mel, *ctx.consts), None, None, None, None
+
+
+class LogmelFunction(torch.autograd.Function):
+    """logmel_op with a gradient: forward dsv_mel_spectrum -> dsv_mel_head; backward dsv_mel_head_backward -> dsv_stft_adjoint (the same padding)
+    -> dsv_mel_clamp_backward (only when the flavour clamps).  x float32 [B][L] -> [B][n_frames][M]."""
+
+    @staticmethod
+    def forward(ctx, x, mb, n_fft, hop, win_length, pl, pr, pad_mode, clamp, mag_eps, floor, log10):
+        adjoint_basis(x.device, n_fft, win_length)            # here, not in backward: a warm-up FORWARD is then enough before a capture
+        S = _spectrum_launch(x, n_fft, hop, win_length, pl, pr, pad_mode, clamp)
+        out, mel = _head_launch(S, mb, mag_eps, floor, log10)
+        ctx.save_for_backward(x, S, mb, mel)
+        ctx.consts = (mag_eps, floor, log10)
+        ctx.geometry = (x.shape[1], n_fft, hop, win_length, pl, pr, pad_mode)
+        ctx.clamp = clamp
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from .stft_loss import _adjoint_launch
+        x, S, mb, mel = ctx.saved_tensors
+        G = _head_backward_launch(S, mb, g.to(torch.float32).contiguous(), mel, *ctx.consts)
+        dx = _adjoint_launch(G, *ctx.geometry)
+        if ctx.clamp:
+            with torch.cuda.device(x.device):
+                _lib.check(_lib.load().dsv_mel_clamp_backward(x.data_ptr(), dx.data_ptr(), dx.data_ptr(), dx.numel(), _stream(x.device)),
+                           'dsv_mel_clamp_backward')
+        return (dx,) + (None,) * 11
+
+
+def spec_logmel_op(spec, mel_basis, *, mag_eps=1e-9, floor=1e-5, log10=False, return_linear_mel=False):
+    """The head of the log-mel analysis on a given spectrum: spec complex64 [B][n_bins][T] (stft_op's result) or float [B][n_bins][T][2],
+    mel_basis [M][n_bins] (M <= 128, data of the caller) -> log(max(mel_basis . sqrt(re^2 + im^2 + mag_eps), floor)) [B][T][M], natural or base
+    10.  All bins are treated alike (an imaginary part stored at bin 0 or n_fft / 2 counts).  Differentiable with respect to `spec` only - one
+    autograd node, one launch each way; the gradient is exactly 0 where the floor is active (it passes at equality) and where the magnitude is
+    0.  A basis that requires grad raises NotImplementedError.  return_linear_mel: also the mel before the logarithm (no gradient)."""
+    if not isinstance(spec, torch.Tensor) or not isinstance(mel_basis, torch.Tensor):
+        raise ValueError('spec_logmel_op: spec and mel_basis must be tensors')
+    if mel_basis.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError('spec_logmel_op: no gradient with respect to the mel basis (detach it)')
+    if mel_basis.dim() != 2 or (mel_basis.shape[1] - 1) * 2 not in SUPPORTED_N_FFT:
+        raise ValueError(f'spec_logmel_op: mel_basis must be [M][n_fft / 2 + 1] with n_fft one of {SUPPORTED_N_FFT}, got {tuple(mel_basis.shape)}')
+    M, n_bins = mel_basis.shape
+    if not 1 <= M <= MAX_MEL_BINS:
+        raise ValueError(f'M={M} mel bins: at most {MAX_MEL_BINS} are supported')
+    if not (floor > 0 and mag_eps >= 0 and np.isfinite(floor) and np.isfinite(mag_eps)):
+        raise ValueError(f'floor={floor} must be > 0 and mag_eps={mag_eps} >= 0, both finite')
+    cplx = spec.is_complex()
+    if cplx:
+        if spec.dim() == 2:
+            spec = spec[None]
+        spec = torch.view_as_real(spec.to(torch.complex64).contiguous())
+    if spec.dim() != 4 or spec.shape[3] != 2 or spec.shape[1] != n_bins or spec.shape[2] < 1 or not 1 <= spec.shape[0] <= 65535:
+        raise ValueError(f'spec_logmel_op: spectrum must be complex [B][{n_bins}][T] or float [B][{n_bins}][T][2] with 1 <= B <= 65535, got '
+                         f'{tuple(spec.shape)}')
+    if not spec.is_cuda or not mel_basis.is_cuda:
+        raise RuntimeError('spec_logmel_op: needs device tensors (there is no CPU path)')
+    S = spec.to(torch.float32).contiguous()
+    mb = mel_basis.detach().to(device=S.device, dtype=torch.float32).contiguous()
+    if S.requires_grad and torch.is_grad_enabled():
+        out, mel = MelHeadFunction.apply(S, mb, float(mag_eps), float(floor), bool(log10))
+    else:
+        out, mel = _head_launch(S, mb, float(mag_eps), float(floor), bool(log10))
+    return (out, mel) if return_linear_mel else out
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

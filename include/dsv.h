@@ -270,6 +270,34 @@ int dsv_spectral_loss(const float* X, const float* Y, float* workspace, float* o
 int dsv_spectral_loss_backward(const float* X, const float* Y, const float* workspace, const float* grad_out, float* G, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------------
+ * Mel loss: the log-mel analysis of modules/hifigan/mel_utils.py:45-76 as a DIFFERENTIABLE chain - the generator's dominant objective
+ * (configs/tts/hifigan.yaml lambda_mel: the L1 distance of two log-mels) - csrc/voc_mel.hpp.  dsv_logmel above is the fused analysis and
+ * has no gradient; here the chain is cut at the spectrum:  dsv_mel_spectrum -> dsv_mel_head,  and back  dsv_mel_head_backward ->
+ * dsv_stft_adjoint -> dsv_mel_clamp_backward.  The L1 mean over the cells is dsf_l1_mean / dsf_l1_mean_bwd (include/dsf.h).  No atomics,
+ * every sum in a fixed order (two calls are bitwise equal); nothing allocates or synchronises: forward and backward record into one graph.
+ * Refused with DSD_ERR_INVALID before any launch: null pointers, n_fft not in {256, 512, 1024, 2048}, M outside [1, 128], T < 1 (or > 2^30),
+ * B outside [1, 65535], mag_eps < 0, floor <= 0 or either not finite, an output that overlaps an input, a spectrum not aligned to 8 bytes.
+ *
+ * dsv_mel_spectrum: dsv_stft's launch (the same kernel, the same bits) with the waveform clamp of dsv_logmel exposed: clamp != 0 reads
+ *   clip(wav, -1, 1).  No lengths, no subtraction.  spec [B][n_fft / 2 + 1][n_frames][2].
+ * dsv_mel_head: spec [B][n_bins][T][2], n_bins = n_fft / 2 + 1, mel_basis [M][n_bins] (data of the caller) ->
+ *       mag = sqrt(re^2 + im^2 + mag_eps);   mel[b][f][m] = sum_k mel_basis[m][k] mag[k][f];   out[b][f][m] = log(max(mel, floor))
+ *   natural (log10 = 0) or base 10, evaluated in float64 and rounded once.  out and mel [B][T][M] are BOTH written (the backward reads mel).  All
+ *   bins are treated alike: whatever imaginary part the caller stored at bins 0 and n_fft / 2 counts.  fp32 MFMA, one launch.
+ * dsv_mel_head_backward: the vector-Jacobian product for a cotangent grad_out [B][T][M], with the forward's spec, mel_basis and mel:
+ *       gm = grad_out / mel [/ ln 10] where mel >= floor, else exactly 0  (torch.clamp(min=)'s rule: the gradient passes at equality)
+ *       G[b][k][f] = (re, im) / mag * sum_m mel_basis[m][k] gm[f][m]      exactly 0 where mag == 0 (only possible with mag_eps = 0)
+ *   G [B][n_bins][T][2], the layout dsv_stft_adjoint takes.  fp32 MFMA, one launch.
+ * dsv_mel_clamp_backward: dx_out[i] = dx_in[i] where -1 <= x[i] <= 1, else 0, over n floats (a NaN x gives 0); dx_out may BE dx_in. */
+int dsv_mel_spectrum(const float* wav, const float* fwd_basis, float* spec, int32_t B, int32_t L, int32_t n_fft, int32_t hop, int32_t pad_l,
+                     int32_t pad_r, int32_t pad_mode, int32_t clamp, void* stream);
+int dsv_mel_head(const float* spec, const float* mel_basis, float* out, float* mel, int32_t B, int32_t T, int32_t n_fft, int32_t M, float mag_eps,
+                 float floor, int32_t log10, void* stream);
+int dsv_mel_head_backward(const float* spec, const float* mel_basis, const float* grad_out, const float* mel, float* G, int32_t B, int32_t T,
+                          int32_t n_fft, int32_t M, float mag_eps, float floor, int32_t log10, void* stream);
+int dsv_mel_clamp_backward(const float* x, const float* dx_in, float* dx_out, int64_t n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
  * PWG discriminator: ParallelWaveGANDiscriminator (modules/parallel_wavegan/models/parallel_wavegan.py:207-300; configs/tts/pwg.yaml
  * discriminator_params: 10 layers, 64 channels, kernel 3, LeakyReLU(0.2)) forward AND backward, and the LSGAN criterion
  * (modules/hifigan/hifigan.py:337-365) - csrc/pwg_disc.hpp.  Activations [B][64][LS(T)] channel-major, waveform-like rows [B][LS(T)]; every call
