@@ -19,6 +19,10 @@ Public surface mirrors the reference's own plugin API for this path:
     avg_pool_op, cond_discriminator_loss
                                         MultiScaleDiscriminator's AvgPool1d(4, 2, 1) on HIP, forward and backward (modules/hifigan/hifigan.py:304)
                                         and hifigan.py:350-356 (diffsinger_amd/hifigan_disc.py)
+    DiscriminatorP, MultiPeriodDiscriminator, disc_p_op, feature_loss, hifigan_adversarial_losses, hifigan_discriminator_losses
+                                        the multi-period discriminator (modules/hifigan/hifigan.py:181-250), forward and backward on HIP, the
+                                        feature-matching loss (:328-334) and the generator's / discriminator's terms against it
+                                        (diffsinger_amd/hifigan_disc.py)
     HifiGanMelLoss, mel_spectrogram_loss_op, spec_logmel_op
                                         the mel-spectrogram loss of the HiFi-GAN trainer (modules/hifigan/mel_utils.py:45-76, lambda_mel) on
                                         the differentiable log-mel (diffsinger_amd/mel_loss.py, diffsinger_amd/stft.py)
@@ -38,6 +42,7 @@ __all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiff
            'ParallelWaveGANDiscriminator', 'pwg_disc_op', 'lsgan_loss_op', 'generator_loss', 'discriminator_loss',
            'pwg_gen_op', 'pwg_generator_losses', 'pwg_discriminator_losses', 'pwg_training_step',
            'avg_pool_op', 'cond_discriminator_loss',
+           'DiscriminatorP', 'MultiPeriodDiscriminator', 'disc_p_op', 'feature_loss', 'hifigan_adversarial_losses', 'hifigan_discriminator_losses',
            'pe_losses', 'pe_training_step',
            'HifiGanMelLoss', 'mel_spectrogram_loss_op', 'spec_logmel_op', 'hifigan_generator_losses', 'hifigan_generator_step']
 
@@ -61,7 +66,8 @@ def __getattr__(name):      # lazy: torch-heavy modules load on first use
     if name in ('pwg_gen_op', 'pwg_generator_losses', 'pwg_discriminator_losses', 'pwg_training_step'):
         from . import pwg_train
         return getattr(pwg_train, name)
-    if name in ('avg_pool_op', 'cond_discriminator_loss'):
+    if name in ('avg_pool_op', 'cond_discriminator_loss', 'DiscriminatorP', 'MultiPeriodDiscriminator', 'disc_p_op', 'feature_loss',
+                'hifigan_adversarial_losses', 'hifigan_discriminator_losses'):
         from . import hifigan_disc
         return getattr(hifigan_disc, name)
     if name in ('pe_losses', 'pe_training_step'):

@@ -50,7 +50,11 @@ SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'ds
                'dsv_pwgt_relu_mask', 'dsv_pwgt_upsample_backward', 'dsv_pwgt_convin_wgrad',
                'dsv_hgt_wgrad_split', 'dsv_hgt_act_floats', 'dsv_hgt_wgrad_workspace_floats', 'dsv_hgt_conv_dgrad', 'dsv_hgt_conv_wgrad', 'dsv_hgt_bias_workspace_floats', 'dsv_hgt_bias_grad',
                'dsv_hgt_upsample_dgrad', 'dsv_hgt_tanh_backward', 'dsv_hgt_noise_conv_backward', 'dsv_hgt_source_mix', 'dsv_hgt_source_backward',
-               'dsv_hgd_pool_samples', 'dsv_hgd_avgpool', 'dsv_hgd_avgpool_backward']
+               'dsv_hgd_pool_samples', 'dsv_hgd_avgpool', 'dsv_hgd_avgpool_backward',
+               'dsv_hgp_height', 'dsv_hgp_folded_samples', 'dsv_hgp_fold', 'dsv_hgp_fold_backward', 'dsv_hgp_edge_workspace_floats', 'dsv_hgp_first',
+               'dsv_hgp_first_backward', 'dsv_hgp_post', 'dsv_hgp_post_backward', 'dsv_hgp_dgrad_phase_taps', 'dsv_hgp_dgrad_packed_offset', 'dsv_hgp_conv',
+               'dsv_hgp_conv_dgrad', 'dsv_hgp_wgrad_splits', 'dsv_hgp_wgrad_workspace_floats', 'dsv_hgp_conv_wgrad', 'dsv_hgp_l1_blocks',
+               'dsv_hgp_l1_partial', 'dsv_hgp_l1_final', 'dsv_hgp_l1_backward']
 
 _fp = C.POINTER(C.c_float)
 _fpp = C.POINTER(C.c_void_p)
@@ -310,6 +314,34 @@ def load():
     lib.dsv_hgd_pool_samples.restype = i32
     lib.dsv_hgd_avgpool.argtypes = [vp, vp, i64, i32, i64, vp]
     lib.dsv_hgd_avgpool_backward.argtypes = [vp, vp, i64, i32, i64, vp]
+    lib.dsv_hgp_height.argtypes = [i32, i32]
+    lib.dsv_hgp_height.restype = i32
+    lib.dsv_hgp_folded_samples.argtypes = [i32, i32]
+    lib.dsv_hgp_folded_samples.restype = i64
+    lib.dsv_hgp_fold.argtypes = [vp, vp, i32, i32, i64, i32, vp]
+    lib.dsv_hgp_fold_backward.argtypes = [vp, vp, i32, i32, i32, vp]
+    lib.dsv_hgp_edge_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
+    lib.dsv_hgp_edge_workspace_floats.restype = i64
+    lib.dsv_hgp_first.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
+    lib.dsv_hgp_first_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.dsv_hgp_post.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.dsv_hgp_post_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]
+    lib.dsv_hgp_dgrad_phase_taps.argtypes = [i32, i32]
+    lib.dsv_hgp_dgrad_phase_taps.restype = i32
+    lib.dsv_hgp_dgrad_packed_offset.argtypes = [i32, i32, i32, i32]
+    lib.dsv_hgp_dgrad_packed_offset.restype = i64
+    lib.dsv_hgp_conv.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]
+    lib.dsv_hgp_conv_dgrad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]
+    lib.dsv_hgp_wgrad_splits.argtypes = [i32, i32, i32, i32, i32]
+    lib.dsv_hgp_wgrad_splits.restype = i32
+    lib.dsv_hgp_wgrad_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
+    lib.dsv_hgp_wgrad_workspace_floats.restype = i64
+    lib.dsv_hgp_conv_wgrad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.dsv_hgp_l1_blocks.argtypes = [i64]
+    lib.dsv_hgp_l1_blocks.restype = i32
+    lib.dsv_hgp_l1_partial.argtypes = [vp, vp, vp, i64, vp]
+    lib.dsv_hgp_l1_final.argtypes = [vp, i32, vp, vp]
+    lib.dsv_hgp_l1_backward.argtypes = [vp, vp, vp, vp, vp, i64, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('dsd_abi_version',):

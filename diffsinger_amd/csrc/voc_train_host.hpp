@@ -20,6 +20,22 @@ static int voc_check_f64_workspace(const char* who, const void* ptr, const char*
 // splits of `len` samples that cover L
 static int voc_splits(int L, int len) { return (L + len - 1) / len; }
 
+// B planes of [H][p] positions of the period discriminator: B and B * p bound the grids, B * H * p <= 2^30 every 32-bit position index
+static bool voc_period_shape_ok(int B, int H, int p) {
+    return B >= 1 && H >= 1 && p >= 1 && p <= 64 && (int64_t)B * p <= 65535 && (int64_t)B * H * p <= ((int64_t)1 << 30);
+}
+static int voc_check_period_shape(const char* who, int B, int H, int p) {
+    if (!voc_period_shape_ok(B, H, p))
+        return fail(DSD_ERR_INVALID, "%s: bad shape (B=%d >= 1, H=%d >= 1, period=%d in [1, 64], B * period <= 65535, B * H * period <= 2^30)", who, B, H, p);
+    return DSD_OK;
+}
+
+// an input range [in, in + n_in) and an output range [out, out + n_out) of floats that must not overlap
+static int voc_check_disjoint(const char* who, const float* in, int64_t n_in, const float* out, int64_t n_out) {
+    if (in < out + n_out && out < in + n_in) return fail(DSD_ERR_INVALID, "%s: input and output overlap", who);
+    return DSD_OK;
+}
+
 // R rows pooled by AvgPool1d(4, 2, 1) from L samples: `in` holds R rows `ld` floats apart of which `in_len` are read, `out` R rows of `out_ld`
 // floats; the two ranges must not overlap
 static int voc_check_pool_rows(const char* who, const float* in, const float* out, int64_t R, int L, int64_t ld, int in_len, int out_ld) {

@@ -1,24 +1,45 @@
-"""HiFi-GAN multi-scale discriminator, the pieces built so far, on the HIP operators of include/dsv.h, section "HiFi-GAN scale discriminator"
-(kernels: csrc/hifigan_disc.hpp).
+"""HiFi-GAN discriminators on the HIP operators of include/dsv.h, sections "HiFi-GAN scale discriminator" (kernels: csrc/hifigan_disc.hpp) and
+"HiFi-GAN period discriminator" (csrc/hifigan_mpd.hpp).
 
     avg_pool_op                                AvgPool1d(4, 2, padding=1) of MultiScaleDiscriminator (modules/hifigan/hifigan.py:304-307), forward
                                                and backward
     generator_loss, discriminator_loss         pwg_disc's (hifigan.py:337-347, :359-365); cond_discriminator_loss hifigan.py:350-356
+    disc_p_op                                  DiscriminatorP (hifigan.py:181-227) on plain weights, forward and backward through ONE autograd node
+    feature_loss                               hifigan.py:328-334
+    DiscriminatorP, MultiPeriodDiscriminator   hifigan.py:181-250: the reference's constructor signatures and state-dict keys
+    hifigan_adversarial_losses, hifigan_discriminator_losses       the generator's adversarial + feature-matching terms, the discriminator's pair
 
-DiscriminatorS itself - the grouped, strided Conv1d stack and the feature-matching loss - is not here: see DESIGN.md section 6 "HiFi-GAN scale
-discriminator".  There is no CPU path.  Nothing here synchronises or reads a device value on the host.
+DiscriminatorS itself - the grouped, strided Conv1d stack - is not here: see DESIGN.md section 6 "HiFi-GAN scale discriminator".  There is no CPU
+path.  Nothing here synchronises or reads a device value on the host, every launch goes to the current stream and the library allocates nothing;
+recording these operators into a torch.cuda.graph is UNVERIFIED (no test or tool does it).
+
+The period discriminator's activations are the reference's tensors, dense [B][C][H][p]: the feature maps disc_p_op returns are views of the buffers
+its kernels wrote, and the module runs d(y) and d(y_hat) as ONE batch of 2 B - every layer's weights stream once per pass - and hands out the two
+halves of each buffer as outputs of the same node.  feature_loss writes the two cotangents of a pair into the halves of one buffer, which the node's
+backward recognises (adjacent addresses) and reads in place: no feature map and no feature-map cotangent is copied on the module's path.
+g * v / ||v|| and its gradient stay torch expressions.
 
 Kernel launches through the library are counted by pwg_disc's counter (`launch_count()` is that function): avg_pool_op is one launch forward
-and one backward - the kernels take the rows of a dense [B][T] tensor as they lie, no padding pass; lsgan_loss_op 2 forward, 1 backward."""
+and one backward; lsgan_loss_op 2 forward, 1 backward.  disc_p_op forward is 15: fold 1, first layer 1, per dense layer 3 (dsv_pack_weight's
+kernel and slack fill, the convolution), conv_post 1.  Its backward is 37 + s + 2 x: conv_post 3 (parameter gradients, their reduction, data
+gradient), per dense layer 1 weight gradient + 1 bias gradient (+ 1 reduction where dsv_hgp_wgrad_splits > 1: s counts those layers), its
+data gradient 2 r + 1 (r = stride: one pack per input phase; 7, 7, 7, 3), the first layer 2, and x = 1 when the input requires a gradient: 2
+more (first layer's data gradient, the fold's adjoint); a layer without a bias is one less.  feature_loss over n pairs is n + 1 forward, n backward."""
 from __future__ import annotations
 
+from typing import List, Optional, Sequence
+
 import torch
+import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
+from . import _lib
+from .pwg import _WN
 from .pwg_disc import _call, _check_x as _check_pwg_x, discriminator_loss, generator_loss, launch_count, lsgan_loss_op
 from .vocoder import padded_samples
 
-__all__ = ['avg_pool_op', 'generator_loss', 'discriminator_loss', 'cond_discriminator_loss', 'launch_count']
+__all__ = ['avg_pool_op', 'generator_loss', 'discriminator_loss', 'cond_discriminator_loss', 'launch_count', 'disc_p_op', 'feature_loss',
+           'DiscriminatorP', 'MultiPeriodDiscriminator', 'hifigan_adversarial_losses', 'hifigan_discriminator_losses', 'period_heights']
 
 
 def _check_x(x, who, min_t=1):
@@ -58,3 +79,339 @@ def cond_discriminator_loss(outputs):
     for dg in outputs:
         loss = loss + lsgan_loss_op(dg, 0.0)
     return loss / len(outputs)
+
+
+# ---- the period discriminator -----------------------------------------------------------------------------------------------------------------
+_CH = (1, 32, 128, 512, 1024, 1024)                              # channels in front of conv l (hifigan.py:193-199); conv_post 1024 -> 1
+_STRIDES = (3, 3, 3, 3, 1)
+_NCONV = 5
+_K, _KPOST = 5, 3
+_PERIODS = (2, 3, 5, 7, 11)
+LRELU_SLOPE = 0.1
+
+
+def period_heights(T: int, period: int):
+    """[H0 .. H4, H4]: the input height of conv l (l = 0..4) and of conv_post, for T samples at this period; ValueError where the reference's
+    reflect pad refuses T (the pad period - T mod period is not shorter than T)"""
+    T, period = int(T), int(period)
+    if period < 1 or T < 1:
+        raise ValueError(f'period_heights: T={T} and period={period} must be >= 1')
+    n_pad = (period - T % period) % period
+    if n_pad >= T:
+        raise ValueError(f'DiscriminatorP: T={T} at period {period} needs a reflect pad of {n_pad} >= T samples')
+    hs = [(T + n_pad) // period]
+    for s in _STRIDES:
+        hs.append((hs[-1] - 1) // s + 1)
+    return hs
+
+
+def _phase_taps(lib, stride, r):
+    m = lib.dsv_hgp_dgrad_phase_taps(stride, r)
+    return [k for k in range(_K) if m >> k & 1]
+
+
+def _f32c(t):
+    return None if t is None else t.to(torch.float32).contiguous()
+
+
+def _join(cr, cg, shape, dev):
+    """the cotangents of the two halves of a buffer of `shape` as (address, what keeps it alive): in place where they are the halves of one
+    buffer (feature_loss's), else joined; (None, None) where neither arrives"""
+    if cr is None and cg is None:
+        return None, None
+    Bh = shape[0] // 2
+    cr, cg = _f32c(cr), _f32c(cg)
+    if cr is not None and cg is not None and cg.data_ptr() == cr.data_ptr() + 4 * cr.numel():
+        return cr.data_ptr(), (cr, cg)
+    t = torch.zeros(shape, device=dev, dtype=torch.float32)
+    if cr is not None:
+        t[:Bh] = cr.reshape(t[:Bh].shape)
+    if cg is not None:
+        t[Bh:] = cg.reshape(t[Bh:].shape)
+    return t.data_ptr(), t
+
+
+class DiscPFunction(torch.autograd.Function):
+    """x [B][1][T], six weights [Co][Ci][K][1], six biases (None where absent) -> (out [B][H p], a_0 .. a_4, a_5 = conv_post's output [B][1][H][p]):
+    views of the node's buffers.  pair=True: B = 2 Bh and every output is handed out as its two halves, (out_r, out_g, the six maps' first halves,
+    the six second halves)."""
+
+    @staticmethod
+    def forward(ctx, x, period, slope, pair, *params):
+        lib = _lib.load()
+        ws, bs = params[:_NCONV + 1], params[_NCONV + 1:]
+        dev = x.device
+        B, _, T = x.shape
+        p = period
+        hs = period_heights(T, p)
+        xf = torch.empty(B, hs[0] * p, device=dev, dtype=torch.float32)
+        _call('dsv_hgp_fold', 1, dev, x.data_ptr(), xf.data_ptr(), B, T, T, p)
+        wd = [w.detach().reshape(w.shape[0], w.shape[1], w.shape[2]).contiguous() for w in ws]
+        b = [None if t is None else t.detach().contiguous() for t in bs]
+        acts = [torch.empty(B, _CH[l + 1], hs[l + 1], p, device=dev, dtype=torch.float32) for l in range(_NCONV)]
+        _call('dsv_hgp_first', 1, dev, xf.data_ptr(), wd[0].data_ptr(), _lib.ptr(b[0]), acts[0].data_ptr(), B, _CH[1], hs[0], p, _STRIDES[0], slope)
+        for l in range(1, _NCONV):
+            ci, co = _CH[l], _CH[l + 1]
+            packed = torch.empty(lib.dsv_packed_floats(co, ci, _K), device=dev, dtype=torch.float32)
+            _call('dsv_pack_weight', 2, dev, wd[l].data_ptr(), co, ci, _K, packed.data_ptr())
+            _call('dsv_hgp_conv', 1, dev, acts[l - 1].data_ptr(), packed.data_ptr(), _lib.ptr(b[l]), acts[l].data_ptr(), B, ci, co, hs[l], p, _STRIDES[l],
+                  slope)
+        post = torch.empty(B, 1, hs[5], p, device=dev, dtype=torch.float32)
+        _call('dsv_hgp_post', 1, dev, acts[4].data_ptr(), wd[5].data_ptr(), _lib.ptr(b[5]), post.data_ptr(), B, _CH[5], hs[5], p)
+        ctx.save_for_backward(xf, *wd, *acts)
+        ctx.meta = (B, T, p, float(slope), bool(pair), hs, [t is not None for t in bs])
+        out = post.view(B, hs[5] * p)
+        maps = acts + [post]
+        if not pair:
+            return (out,) + tuple(maps)
+        Bh = B // 2
+        return (out[:Bh], out[Bh:]) + tuple(m[:Bh] for m in maps) + tuple(m[Bh:] for m in maps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *cots):
+        lib = _lib.load()
+        xf, *rest = ctx.saved_tensors
+        wd, acts = rest[:_NCONV + 1], rest[_NCONV + 1:]
+        B, T, p, slope, pair, hs, has_b = ctx.meta
+        dev = xf.device
+        keep = []                                               # tensors whose addresses are in flight
+        if pair:
+            g_out, k = _join(cots[0], cots[1], (B, hs[5] * p), dev)
+            keep.append(k)
+            cot = []
+            for l in range(_NCONV + 1):
+                a, k = _join(cots[2 + l], cots[2 + _NCONV + 1 + l], (B, _CH[l + 1] if l < _NCONV else 1, hs[l + 1] if l < _NCONV else hs[5], p), dev)
+                cot.append(a); keep.append(k)
+        else:
+            t = _f32c(cots[0])
+            g_out = None if t is None else t.data_ptr()
+            keep.append(t)
+            cot = []
+            for l in range(_NCONV + 1):
+                t = _f32c(cots[1 + l])
+                cot.append(None if t is None else t.data_ptr()); keep.append(t)
+        gp1, gp2 = (g_out, cot[5]) if g_out is not None else (cot[5], None)
+        if gp1 is None:                                         # nothing arrives on the output: its cotangent is zero
+            z = torch.zeros(B, hs[5] * p, device=dev, dtype=torch.float32)
+            keep.append(z)
+            gp1 = z.data_ptr()
+        dws: List[Optional[torch.Tensor]] = [None] * (_NCONV + 1)
+        dbs: List[Optional[torch.Tensor]] = [None] * (_NCONV + 1)
+
+        def grads(l, co, ci, k):
+            dws[l] = torch.empty(co, ci, k, 1, device=dev, dtype=torch.float32)
+            dbs[l] = torch.empty(co, device=dev, dtype=torch.float32) if has_b[l] else None
+
+        grads(5, 1, _CH[5], _KPOST)
+        ws_e = torch.empty(max(lib.dsv_hgp_edge_workspace_floats(B, hs[5], p, _CH[5], _KPOST), lib.dsv_hgp_edge_workspace_floats(B, hs[1], p, _CH[1], _K)),
+                           device=dev, dtype=torch.float32)
+        G = torch.empty(B, _CH[5], hs[5], p, device=dev, dtype=torch.float32)
+        _call('dsv_hgp_post_backward', 3, dev, gp1, gp2, acts[4].data_ptr(), wd[5].data_ptr(), cot[4], ws_e.data_ptr(), dws[5].data_ptr(), _lib.ptr(dbs[5]),
+              G.data_ptr(), B, _CH[5], hs[5], p, slope)
+        for l in range(_NCONV - 1, 0, -1):
+            ci, co, S = _CH[l], _CH[l + 1], _STRIDES[l]
+            grads(l, co, ci, _K)
+            nws = lib.dsv_hgp_wgrad_workspace_floats(B, ci, co, hs[l + 1], p)
+            ws_w = torch.empty(nws, device=dev, dtype=torch.float32) if nws else None
+            _call('dsv_hgp_conv_wgrad', 1 + (1 if nws else 0) + (1 if has_b[l] else 0), dev, G.data_ptr(), acts[l - 1].data_ptr(), _lib.ptr(ws_w),
+                  dws[l].data_ptr(), _lib.ptr(dbs[l]), B, ci, co, hs[l], p, S)
+            packed = torch.empty(lib.dsv_hgp_dgrad_packed_offset(ci, co, S, S), device=dev, dtype=torch.float32)
+            for r in range(S):
+                ks = _phase_taps(lib, S, r)
+                m = wd[l][:, :, ks].permute(1, 0, 2).contiguous()                      # [ci][co][taps of the phase]
+                _call('dsv_pack_weight', 2, dev, m.data_ptr(), ci, co, len(ks), packed.data_ptr() + 4 * lib.dsv_hgp_dgrad_packed_offset(ci, co, S, r))
+            Gn = torch.empty(B, ci, hs[l], p, device=dev, dtype=torch.float32)
+            _call('dsv_hgp_conv_dgrad', 1, dev, G.data_ptr(), packed.data_ptr(), cot[l - 1], acts[l - 1].data_ptr(), Gn.data_ptr(), B, ci, co, hs[l], p, S,
+                  slope)
+            G = Gn
+        grads(0, _CH[1], 1, _K)
+        need_dx = ctx.needs_input_grad[0]
+        dxf = torch.empty(B, hs[0] * p, device=dev, dtype=torch.float32) if need_dx else None
+        _call('dsv_hgp_first_backward', 3 if need_dx else 2, dev, G.data_ptr(), xf.data_ptr(), wd[0].data_ptr(), ws_e.data_ptr(), dws[0].data_ptr(),
+              _lib.ptr(dbs[0]), _lib.ptr(dxf), B, _CH[1], hs[0], p, _STRIDES[0])
+        gx = None
+        if need_dx:
+            dx = torch.empty(B, T, device=dev, dtype=torch.float32)
+            _call('dsv_hgp_fold_backward', 1, dev, dxf.data_ptr(), dx.data_ptr(), B, T, p)
+            gx = dx[:, None, :]
+        del keep
+        return (gx, None, None, None) + tuple(dws) + tuple(dbs)
+
+
+def _check_px(x, period, who):
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f'{who}: x must be a tensor')
+    if x.dim() != 3 or x.shape[1] != 1 or x.shape[0] < 1 or x.shape[2] < 1:
+        raise ValueError(f'{who}: x must be [B][1][T] with B >= 1 and T >= 1, got {tuple(x.shape)}')
+    if not isinstance(period, int) or not 1 <= period <= 64:
+        raise ValueError(f'{who}: period={period!r} must be an integer in [1, 64]')
+    hs = period_heights(x.shape[2], period)
+    _check_pwg_x(x, who)
+    if x.shape[0] * period > 65535:
+        raise ValueError(f'{who}: B * period = {x.shape[0] * period} exceeds 65535')
+    return hs
+
+
+def _check_params(x, weights, biases, slope, who):
+    if len(weights) != _NCONV + 1 or len(biases) != _NCONV + 1:
+        raise ValueError(f'{who}: six weights and six biases (None where absent), got {len(weights)} and {len(biases)}')
+    if not 0.0 < float(slope) < 1.0:
+        raise ValueError(f'{who}: slope={slope} must be in (0, 1)')
+    for i, w in enumerate(weights):
+        want = (_CH[i + 1], _CH[i], _K, 1) if i < _NCONV else (1, _CH[_NCONV], _KPOST, 1)
+        if not isinstance(w, torch.Tensor) or tuple(w.shape) != want or w.dtype != torch.float32 or w.device != x.device:
+            raise ValueError(f'{who}: weights[{i}] must be float32 {want} on {x.device}')
+        bi = biases[i]
+        if bi is not None and (tuple(bi.shape) != (want[0],) or bi.dtype != torch.float32 or bi.device != x.device):
+            raise ValueError(f'{who}: biases[{i}] must be float32 ({want[0]},) on {x.device}, got {bi.dtype} {tuple(bi.shape)} on {bi.device}')
+
+
+def disc_p_op(x, period: int, weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]], slope: float = LRELU_SLOPE):
+    """DiscriminatorP.forward on plain weights: weights[l] [Co][Ci][5][1] for the five convs (1 -> 32 -> 128 -> 512 -> 1024 -> 1024, stride 3, 3, 3, 3,
+    1), weights[5] [1][1024][3][1]; biases[l] [Co] or None; x float32 [B][1][T] on the device -> (out [B][H p], fmap): the six feature maps
+    [B][C][H_l][p], views of the node's own buffers (fmap[5] and out are the same values).  Differentiable with respect to x, every weight and
+    every bias; cotangents are accepted on out and on every map."""
+    _check_px(x, period, 'disc_p_op')
+    _check_params(x, weights, biases, slope, 'disc_p_op')
+    res = DiscPFunction.apply(x.contiguous(), period, float(slope), False, *weights, *biases)
+    return res[0], list(res[1:])
+
+
+def _disc_p_pair(yy, period, weights, biases, slope):
+    """disc_p_op over cat(y, y_hat): ((out_r, fmap_r), (out_g, fmap_g)), every tensor a half of the node's buffers"""
+    res = DiscPFunction.apply(yy, period, float(slope), True, *weights, *biases)
+    n = _NCONV + 1
+    return (res[0], list(res[2:2 + n])), (res[1], list(res[2 + n:]))
+
+
+class FeatureLossFunction(torch.autograd.Function):
+    """n, r_0 .. r_{n-1}, g_0 .. g_{n-1} (float32, contiguous, pairwise equal shapes) -> 0-dim 2 sum_i mean|r_i - g_i|"""
+
+    @staticmethod
+    def forward(ctx, n, *ts):
+        lib = _lib.load()
+        dev = ts[0].device
+        blocks = [lib.dsv_hgp_l1_blocks(t.numel()) for t in ts[:n]]
+        ws = torch.empty(sum(blocks), device=dev, dtype=torch.float64)
+        off = 0
+        for i in range(n):
+            _call('dsv_hgp_l1_partial', 1, dev, ts[i].data_ptr(), ts[n + i].data_ptr(), ws.data_ptr() + 8 * off, ts[i].numel())
+            off += blocks[i]
+        out = torch.empty(1, device=dev, dtype=torch.float32)
+        _call('dsv_hgp_l1_final', 1, dev, ws.data_ptr(), off, out.data_ptr())
+        ctx.save_for_backward(*ts)
+        ctx.n = n
+        return out.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        ts, n = ctx.saved_tensors, ctx.n
+        g = g.to(torch.float32).reshape(1).contiguous()
+        dr, dg = [], []
+        for i in range(n):
+            buf = torch.empty((2,) + tuple(ts[i].shape), device=g.device, dtype=torch.float32)      # the two cotangents, adjacent: DiscPFunction reads them in place
+            _call('dsv_hgp_l1_backward', 1, g.device, ts[i].data_ptr(), ts[n + i].data_ptr(), g.data_ptr(), buf[0].data_ptr(), buf[1].data_ptr(),
+                  ts[i].numel())
+            dr.append(buf[0]); dg.append(buf[1])
+        return (None,) + tuple(dr) + tuple(dg)
+
+
+def feature_loss(fmap_r, fmap_g):
+    """modules/hifigan/hifigan.py:328-334: 2 * the sum over the discriminators and their maps of mean|r - g| -> 0-dim float32; float64 sums in a fixed
+    order.  fmap_r, fmap_g: lists of lists of float32 device tensors of pairwise equal shapes (a discriminator's maps, or any tensors)."""
+    rs = [t for d in fmap_r for t in d]
+    gs = [t for d in fmap_g for t in d]
+    if not rs or len(rs) != len(gs):
+        raise ValueError(f'feature_loss: as many real as generated maps, at least one; got {len(rs)} and {len(gs)}')
+    for i, (r, g) in enumerate(zip(rs, gs)):
+        for t in (r, g):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.numel() < 1:
+                what = f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f'feature_loss: map {i} must be a non-empty float32 device tensor (there is no CPU path), got {what}')
+        if r.shape != g.shape or r.device != g.device:
+            raise ValueError(f'feature_loss: map {i}: {tuple(r.shape)} on {r.device} against {tuple(g.shape)} on {g.device}')
+    return FeatureLossFunction.apply(len(rs), *[t.contiguous() for t in rs], *[t.contiguous() for t in gs])
+
+
+class DiscriminatorP(nn.Module):
+    """modules/hifigan/hifigan.py:181-227.  forward(x [B,1,T], mel=None) -> (out [B, H p], fmap: six maps [B, C, H_l, p]), differentiable with respect
+    to x and every parameter.  convs[l] / conv_post hold weight_g [Co,1,1,1], weight_v [Co,Ci,K,1], bias (or weight after remove_weight_norm())."""
+
+    def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False, use_cond=False, c_in=1):
+        super().__init__()
+        bad = []
+        if use_cond:
+            bad.append('use_cond (the mel-conditioned input)')
+        if c_in != 1:
+            bad.append('c_in other than 1')
+        if use_spectral_norm:
+            bad.append('spectral norm')
+        if kernel_size != _K or stride != 3:
+            bad.append('kernel_size / stride other than 5 / 3')
+        if bad:
+            raise NotImplementedError('DiscriminatorP on HIP covers the shipped configuration only: ' + '; '.join(bad))
+        if not isinstance(period, int) or not 1 <= period <= 64:
+            raise ValueError(f'DiscriminatorP: period={period!r} must be an integer in [1, 64]')
+        self.period, self.use_cond = period, False
+        self.convs = nn.ModuleList([_WN((_CH[l + 1], _CH[l], _K, 1), True, True) for l in range(_NCONV)])
+        self.conv_post = _WN((1, _CH[_NCONV], _KPOST, 1), True, True)
+
+    def remove_weight_norm(self):
+        for m in self.modules():
+            if isinstance(m, _WN):
+                m.remove_weight_norm()
+
+    def _params(self):
+        mods = list(self.convs) + [self.conv_post]
+        return [torch._weight_norm(m.weight_v, m.weight_g, 0) if hasattr(m, 'weight_g') else m.weight for m in mods], [m.bias for m in mods]
+
+    def forward(self, x, mel=None):
+        if mel is not None:
+            raise NotImplementedError('DiscriminatorP on HIP: use_cond (a mel input) is not supported')
+        ws, bs = self._params()
+        return disc_p_op(x, self.period, ws, bs, LRELU_SLOPE)
+
+
+class MultiPeriodDiscriminator(nn.Module):
+    """modules/hifigan/hifigan.py:230-250: periods 2, 3, 5, 7, 11.  forward(y, y_hat, mel=None) -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs).  d(y) and
+    d(y_hat) run as one batch of 2 B per period (weight norm has no per-call state: the two calls of the reference use identical weights)."""
+
+    def __init__(self, use_cond=False, c_in=1):
+        super().__init__()
+        self.discriminators = nn.ModuleList([DiscriminatorP(p, use_cond=use_cond, c_in=c_in) for p in _PERIODS])
+
+    def remove_weight_norm(self):
+        for d in self.discriminators:
+            d.remove_weight_norm()
+
+    def forward(self, y, y_hat, mel=None):
+        if mel is not None:
+            raise NotImplementedError('MultiPeriodDiscriminator on HIP: use_cond (a mel input) is not supported')
+        for d in self.discriminators:
+            _check_px(y, d.period, 'MultiPeriodDiscriminator')
+        _check_pwg_x(y_hat, 'MultiPeriodDiscriminator')
+        if y_hat.shape != y.shape or y_hat.device != y.device:
+            raise ValueError(f'MultiPeriodDiscriminator: y {tuple(y.shape)} on {y.device} against y_hat {tuple(y_hat.shape)} on {y_hat.device}')
+        yy = torch.cat([y, y_hat]).contiguous()
+        rs, gs, frs, fgs = [], [], [], []
+        for d in self.discriminators:
+            ws, bs = d._params()
+            _check_params(yy, ws, bs, LRELU_SLOPE, 'MultiPeriodDiscriminator')
+            (r, fr), (g, fg) = _disc_p_pair(yy, d.period, ws, bs, LRELU_SLOPE)
+            rs.append(r); gs.append(g); frs.append(fr); fgs.append(fg)
+        return rs, gs, frs, fgs
+
+
+def hifigan_adversarial_losses(disc, y, y_hat):
+    """the generator's terms against `disc` (a MultiPeriodDiscriminator): dict(adv = generator_loss(d(y_hat)), fm = feature_loss(fmaps of y, of
+    y_hat)); gradients flow to y_hat (and to the discriminator's parameters, which a generator step does not update)"""
+    _, gs, frs, fgs = disc(y, y_hat)
+    return dict(adv=generator_loss(gs), fm=feature_loss(frs, fgs))
+
+
+def hifigan_discriminator_losses(disc, y, y_hat):
+    """the discriminator's pair (r_loss, g_loss) = discriminator_loss(d(y), d(y_hat.detach()))"""
+    rs, gs, _, _ = disc(y, y_hat.detach())
+    return discriminator_loss(rs, gs)

@@ -461,6 +461,60 @@ int32_t dsv_hgd_pool_samples(int32_t L);
 int dsv_hgd_avgpool(const float* x, float* out, int64_t R, int32_t L, int64_t ld_x, void* stream);
 int dsv_hgd_avgpool_backward(const float* g, float* dx, int64_t R, int32_t L, int64_t ld_g, void* stream);
 
+/* HiFi-GAN period discriminator: DiscriminatorP (modules/hifigan/hifigan.py:181-227) forward and backward, and the feature-matching L1
+ * (hifigan.py:328-334) - csrc/hifigan_mpd.hpp.  No atomics, a fixed order of additions (two calls are bitwise equal; a forward value does not depend
+ * on the batch it is computed in); nothing allocates, synchronises or reads a device value on the host; everything is enqueued on `stream`; bad
+ * shapes are refused with DSD_ERR_INVALID before any launch, as are overlapping input and output ranges.
+ * LAYOUT: every activation is the reference's tensor, dense [B][C][H][period] float32 - no padding, no tail; a convolution runs along H only.
+ *   Shapes: B >= 1, H >= 1, period in [1, 64], B * period <= 65535, B * H * period <= 2^30.  Heights: dsv_hgp_height(H, stride) = (H - 1) / stride + 1
+ *   (kernel 5, padding 2).  stride is 1 or 3.
+ * dsv_hgp_folded_samples(T, period): T rounded up to a multiple of the period, -1 where the reflect pad would not be shorter than T.
+ * dsv_hgp_fold: F.pad(x, (0, Tp - T), 'reflect') of x, B rows ld_x >= T floats apart (nothing is read beyond sample T of a row) -> out [B][Tp],
+ *   which IS [B][1][Tp / period][period].  dsv_hgp_fold_backward: g [B][Tp] -> dx [B][T]; a reflected sample's gradient adds into its source.
+ * dsv_hgp_first: x [B][1][H][period], w [C][5], bias [C] or NULL -> out = leaky_relu(conv) [B][C][Ho][period].  dsv_hgp_first_backward: g0 the
+ *   gradient with respect to the pre-activation -> dw [C][5], db [C] or NULL, dx [B][H][period] or NULL; workspace: dsv_hgp_edge_workspace_floats(B,
+ *   Ho, period, C, 5) floats.
+ * dsv_hgp_conv: a dense layer on MFMA, x [B][Ci][H][period], w_packed = dsv_pack_weight of [Co][Ci][5] (rows Co, Ci, KT 5), bias [Co] or NULL ->
+ *   out = leaky_relu(conv) [B][Co][Ho][period]; Ci and Co multiples of 32.
+ * dsv_hgp_conv_dgrad: g [B][Co][Ho][period] -> out [B][Ci][H][period] = (W^T g + cot) * mask(saved): cot (the cotangent arriving on the feature map
+ *   below) and saved (that feature map: mask 1 where > 0, else slope) may be NULL.  Polyphase: w_packed holds, for every input phase r < stride, at
+ *   float offset dsv_hgp_dgrad_packed_offset(Ci, Co, stride, r), dsv_pack_weight (rows Ci, Co, KT = number of taps) of [Ci][Co][taps] with
+ *   [ci][co][t] = W[co][ci][k_t], k_t the set bits of dsv_hgp_dgrad_phase_taps(stride, r) in ascending order; offset(.., stride) is the buffer's size.
+ * dsv_hgp_conv_wgrad: dw [Co][Ci][5] = sum over positions of g x, db [Co] (or NULL) = sum of g.  dsv_hgp_wgrad_splits(B, Ci, Co, Ho, period) splits
+ *   of the position axis (1: no workspace, the output tiles fill the chip); workspace: dsv_hgp_wgrad_workspace_floats(..) floats (0 for one split).
+ * dsv_hgp_post: a [B][C][H][period], w [C][3], bias [1] or NULL -> out [B][H][period] (kernel 3, stride 1, padding 1).  dsv_hgp_post_backward: gp
+ *   (+ gp2 when not NULL: the cotangents of the flattened output and of the last feature map) -> dw [C][3], db [1] or NULL, ga [B][C][H][period] =
+ *   (W^T gp + cot) * mask(a); workspace: dsv_hgp_edge_workspace_floats(B, H, period, C, 3).
+ * dsv_hgp_l1_partial: dsv_hgp_l1_blocks(n) float64 partial sums of |r - g| / n into workspace (8-byte aligned); dsv_hgp_l1_final: out[0] = 2 * the
+ *   sum of nblocks partials (every pair's, laid out one after the other).  dsv_hgp_l1_backward: dr = 2 sign(r - g) / n * grad_out[0], dg = -dr;
+ *   sign(0) = 0. */
+int32_t dsv_hgp_height(int32_t H, int32_t stride);
+int64_t dsv_hgp_folded_samples(int32_t T, int32_t period);
+int dsv_hgp_fold(const float* x, float* out, int32_t B, int32_t T, int64_t ld_x, int32_t period, void* stream);
+int dsv_hgp_fold_backward(const float* g, float* dx, int32_t B, int32_t T, int32_t period, void* stream);
+int64_t dsv_hgp_edge_workspace_floats(int32_t B, int32_t H, int32_t period, int32_t C, int32_t K);
+int dsv_hgp_first(const float* x, const float* w, const float* bias, float* out, int32_t B, int32_t C, int32_t H, int32_t period, int32_t stride,
+                  float slope, void* stream);
+int dsv_hgp_first_backward(const float* g0, const float* x, const float* w, float* workspace, float* dw, float* db, float* dx, int32_t B, int32_t C,
+                           int32_t H, int32_t period, int32_t stride, void* stream);
+int dsv_hgp_post(const float* a, const float* w, const float* bias, float* out, int32_t B, int32_t C, int32_t H, int32_t period, void* stream);
+int dsv_hgp_post_backward(const float* gp, const float* gp2, const float* a, const float* w, const float* cot, float* workspace, float* dw, float* db,
+                          float* ga, int32_t B, int32_t C, int32_t H, int32_t period, float slope, void* stream);
+int32_t dsv_hgp_dgrad_phase_taps(int32_t stride, int32_t phase);
+int64_t dsv_hgp_dgrad_packed_offset(int32_t Ci, int32_t Co, int32_t stride, int32_t phase);
+int dsv_hgp_conv(const float* x, const float* w_packed, const float* bias, float* out, int32_t B, int32_t Ci, int32_t Co, int32_t H, int32_t period,
+                 int32_t stride, float slope, void* stream);
+int dsv_hgp_conv_dgrad(const float* g, const float* w_packed, const float* cot, const float* saved, float* out, int32_t B, int32_t Ci, int32_t Co,
+                       int32_t H, int32_t period, int32_t stride, float slope, void* stream);
+int32_t dsv_hgp_wgrad_splits(int32_t B, int32_t Ci, int32_t Co, int32_t H_out, int32_t period);
+int64_t dsv_hgp_wgrad_workspace_floats(int32_t B, int32_t Ci, int32_t Co, int32_t H_out, int32_t period);
+int dsv_hgp_conv_wgrad(const float* g, const float* x, float* workspace, float* dw, float* db, int32_t B, int32_t Ci, int32_t Co, int32_t H,
+                       int32_t period, int32_t stride, void* stream);
+int32_t dsv_hgp_l1_blocks(int64_t n);
+int dsv_hgp_l1_partial(const float* r, const float* g, void* workspace, int64_t n, void* stream);
+int dsv_hgp_l1_final(const void* workspace, int32_t nblocks, float* out, void* stream);
+int dsv_hgp_l1_backward(const float* r, const float* g, const float* grad_out, float* dr, float* dg, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
