@@ -26,9 +26,15 @@ Public surface mirrors the reference's own plugin API for this path:
     HifiGanMelLoss, mel_spectrogram_loss_op, spec_logmel_op
                                         the mel-spectrogram loss of the HiFi-GAN trainer (modules/hifigan/mel_utils.py:45-76, lambda_mel) on
                                         the differentiable log-mel (diffsinger_amd/mel_loss.py, diffsinger_amd/stft.py)
-    hifigan_generator_losses, hifigan_generator_step
+    hifigan_generator_losses, hifigan_generator_step, hifigan_training_step
                                         the mel term of the HiFi-GAN generator objective and one step on it, on
-                                        HifiGanGenerator.forward_train (diffsinger_amd/hifigan_train.py); no adversarial term yet
+                                        HifiGanGenerator.forward_train; the full step with the adversarial and feature-matching terms
+                                        against a list of discriminators, and their own objective (diffsinger_amd/hifigan_train.py)
+    MultiTensorOptimizer, RAdam, AdamW, pwg_optimizers
+                                        the vocoder rows' optimisers on HIP: one update over the list of parameter tensors with the
+                                        global-norm clip folded in (clip_and_step); RAdam in the arithmetic of
+                                        modules/parallel_wavegan/optimizers/radam.py, AdamW, and the RAdam + StepLR pairs of
+                                        configs/tts/pwg.yaml (diffsinger_amd/voc_optim.py)
     pe_losses(output, sample, hp), pe_training_step(model, sample, hp)
                                         PitchExtractionTask.run_model / ._training_step (tasks/tts/pe.py:111-155) on the HIP PitchExtractor
                                         (diffsinger_amd/pe.py)
@@ -44,7 +50,8 @@ __all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiff
            'avg_pool_op', 'cond_discriminator_loss',
            'DiscriminatorP', 'MultiPeriodDiscriminator', 'disc_p_op', 'feature_loss', 'hifigan_adversarial_losses', 'hifigan_discriminator_losses',
            'pe_losses', 'pe_training_step',
-           'HifiGanMelLoss', 'mel_spectrogram_loss_op', 'spec_logmel_op', 'hifigan_generator_losses', 'hifigan_generator_step']
+           'HifiGanMelLoss', 'mel_spectrogram_loss_op', 'spec_logmel_op', 'hifigan_generator_losses', 'hifigan_generator_step',
+           'hifigan_training_step', 'MultiTensorOptimizer', 'RAdam', 'AdamW', 'pwg_optimizers']
 
 
 def __getattr__(name):      # lazy: torch-heavy modules load on first use
@@ -79,7 +86,10 @@ def __getattr__(name):      # lazy: torch-heavy modules load on first use
     if name == 'spec_logmel_op':
         from .stft import spec_logmel_op
         return spec_logmel_op
-    if name in ('hifigan_generator_losses', 'hifigan_generator_step'):
+    if name in ('hifigan_generator_losses', 'hifigan_generator_step', 'hifigan_training_step'):
         from . import hifigan_train
         return getattr(hifigan_train, name)
+    if name in ('MultiTensorOptimizer', 'RAdam', 'AdamW', 'pwg_optimizers'):
+        from . import voc_optim
+        return getattr(voc_optim, name)
     raise AttributeError(name)

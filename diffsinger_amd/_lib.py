@@ -54,7 +54,9 @@ SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'ds
                'dsv_hgp_height', 'dsv_hgp_folded_samples', 'dsv_hgp_fold', 'dsv_hgp_fold_backward', 'dsv_hgp_edge_workspace_floats', 'dsv_hgp_first',
                'dsv_hgp_first_backward', 'dsv_hgp_post', 'dsv_hgp_post_backward', 'dsv_hgp_dgrad_phase_taps', 'dsv_hgp_dgrad_packed_offset', 'dsv_hgp_conv',
                'dsv_hgp_conv_dgrad', 'dsv_hgp_wgrad_splits', 'dsv_hgp_wgrad_workspace_floats', 'dsv_hgp_conv_wgrad', 'dsv_hgp_l1_blocks',
-               'dsv_hgp_l1_partial', 'dsv_hgp_l1_final', 'dsv_hgp_l1_backward']
+               'dsv_hgp_l1_partial', 'dsv_hgp_l1_final', 'dsv_hgp_l1_backward',
+               'dsv_mt_chunk_floats', 'dsv_mt_table_tensors', 'dsv_mt_table_chunks', 'dsv_mt_set_table_limit', 'dsv_mt_workspace_floats', 'dsv_mt_grad_norm',
+               'dsv_radam_scalars', 'dsv_mt_radam_step', 'dsv_mt_adamw_step']
 
 _fp = C.POINTER(C.c_float)
 _fpp = C.POINTER(C.c_void_p)
@@ -342,6 +344,17 @@ def load():
     lib.dsv_hgp_l1_partial.argtypes = [vp, vp, vp, i64, vp]
     lib.dsv_hgp_l1_final.argtypes = [vp, i32, vp, vp]
     lib.dsv_hgp_l1_backward.argtypes = [vp, vp, vp, vp, vp, i64, vp]
+    f64 = C.c_double
+    for name in ('dsv_mt_chunk_floats', 'dsv_mt_table_tensors', 'dsv_mt_table_chunks'):
+        getattr(lib, name).argtypes = []
+        getattr(lib, name).restype = i32
+    lib.dsv_mt_set_table_limit.argtypes = [i32, i32]
+    lib.dsv_mt_workspace_floats.argtypes = [vp, i64]
+    lib.dsv_mt_workspace_floats.restype = i64
+    lib.dsv_mt_grad_norm.argtypes = [vp, vp, i64, f64, vp, i64, vp, vp]
+    lib.dsv_radam_scalars.argtypes = [i64, f64, f64, vp]
+    lib.dsv_mt_radam_step.argtypes = [vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i64, vp, vp]
+    lib.dsv_mt_adamw_step.argtypes = [vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i64, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ('dsd_abi_version',):

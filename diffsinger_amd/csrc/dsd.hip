@@ -1450,3 +1450,4 @@ extern "C" int dsd_debug_layer_timeline(dsd_handle* h, int32_t layer, int32_t t,
 #include "hifigan_disc.hpp"
 #include "hifigan_mpd_abi.hpp"
 #include "pe_train.hpp"
+#include "voc_optim_abi.hpp"

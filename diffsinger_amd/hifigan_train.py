@@ -4,8 +4,11 @@ csrc/hifigan_train.hpp).
     hifigan_gen_op      the generator on plain weights, forward and backward through ONE autograd node (HifiGanGenFunction);
                         HifiGanGenerator.forward_train applies the weight-norm expression in torch and calls it
     hifigan_generator_losses, hifigan_generator_step
-                        the mel term of the generator objective (lambda_mel * HifiGanMelLoss, diffsinger_amd/mel_loss.py) and one step on it;
-                        the adversarial and feature-matching terms are not built
+                        the mel term of the generator objective (lambda_mel * HifiGanMelLoss, diffsinger_amd/mel_loss.py) and one step on it
+    hifigan_training_step
+                        the full step: lambda_mel * mel + the adversarial and feature-matching terms against a list of discriminators
+                        (diffsinger_amd/hifigan_disc.py), then the discriminators' objective on the detached waveform; optimisers:
+                        diffsinger_amd/voc_optim.py (AdamW with adam_b1 / adam_b2) or any torch optimiser
 
 The forward is the inference path's one-launch-per-convolution form (dsv_conv1d / dsv_conv1d_folded, bit-identical to the fused chains, DESIGN.md
 section 6): every convolution's input is a tensor in memory and the leaky ReLU in front of it is applied while the kernel stages it, so the saved
@@ -23,9 +26,10 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from .voc_optim import MultiTensorOptimizer
 from .vocoder import LRELU_SLOPE, MAX_REACH, _HipOps, fold_weight, get_padding, padded_samples, polyphase_weight
 
-__all__ = ['hifigan_gen_op', 'param_layout', 'hifigan_generator_losses', 'hifigan_generator_step']
+__all__ = ['hifigan_gen_op', 'param_layout', 'hifigan_generator_losses', 'hifigan_generator_step', 'hifigan_training_step']
 
 POST_SLOPE = 0.01                  # F.leaky_relu's default slope in front of conv_post (hifigan.py:167)
 SINE_AMP, NOISE_STD, VOICED_THRESHOLD = 0.1, 0.003, 0.0
@@ -309,8 +313,8 @@ def hifigan_gen_op(x, f0, rand_ini, noise, h, params, *, return_saved=False):
 def hifigan_generator_losses(gen, mel_loss, x, f0, y, *, lambda_mel, rand_ini=None, noise=None):
     """The mel term of the HiFi-GAN generator objective (configs/tts/hifigan.yaml lambda_mel): y_hat = gen.forward_train(x, f0) on the given
     source draws, mel = mel_loss(y_hat, y) (diffsinger_amd.mel_loss.HifiGanMelLoss; y the recording [B][1][L] or [B][L]), total = lambda_mel * mel.
-    The adversarial and the feature-matching terms of the reference's generator objective are NOT part of it: the discriminators are not
-    trained on this path yet.  -> (dict(mel, total), y_hat)"""
+    The adversarial and the feature-matching terms of the reference's generator objective are NOT part of it: hifigan_training_step adds
+    them.  -> (dict(mel, total), y_hat)"""
     y_hat = gen.forward_train(x, f0, rand_ini=rand_ini, noise=noise)
     mel = mel_loss(y_hat, y)
     return {'mel': mel, 'total': lambda_mel * mel}, y_hat
@@ -329,8 +333,59 @@ def hifigan_generator_step(gen, mel_loss, batch, hp, opt_g=None):
                                          rand_ini=batch.get('rand_ini'), noise=batch.get('noise'))
     losses['total'].backward()
     out = {'gen_' + k: v.detach() for k, v in losses.items()}
-    clip = hp.get('generator_grad_norm')
-    out['gen_grad_norm'] = torch.nn.utils.clip_grad_norm_(gparams, float('inf') if clip is None else clip)
-    if opt_g is not None:
-        opt_g.step()
+    out['gen_grad_norm'] = _clip_and_step(gparams, hp.get('generator_grad_norm'), opt_g)
+    return out
+
+
+def _clip_and_step(params, max_norm, opt):
+    """clip_grad_norm_(params, max_norm; None: no clipping) and opt.step() when an optimiser is given -> the norm before clipping.  A
+    voc_optim.MultiTensorOptimizer does both itself over ITS parameters, without reading the norm on the host (.grad stays unscaled)."""
+    max_norm = float('inf') if max_norm is None else max_norm
+    if isinstance(opt, MultiTensorOptimizer):
+        return opt.clip_and_step(max_norm)
+    norm = torch.nn.utils.clip_grad_norm_(params, max_norm)
+    if opt is not None:
+        opt.step()
+    return norm
+
+
+def hifigan_training_step(gen, discs, mel_loss, batch, hp, opt_g=None, opt_d=None):
+    """One step of the HiFi-GAN trainer in the shape of pwg_training_step.  `discs`: a list of modules with MultiPeriodDiscriminator's
+    forward(y, y_hat) -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs); batch and hp as hifigan_generator_step takes them, hp optionally with
+    discriminator_grad_norm; opt_d steps the parameters of every module of `discs`.
+    Generator: total = lambda_mel * mel + sum over discs of (adv + fm) (hifigan_generator_losses' parts and hifigan_adversarial_losses), its
+    backward, the clip (only when hp carries generator_grad_norm), opt_g's step when given.  Then the discriminators: the gradients the generator's
+    terms left on them are dropped, total = sum over discs of (real + fake) of hifigan_discriminator_losses on the detached waveform, its
+    backward, the clip at discriminator_grad_norm when given, opt_d's step.  With an empty `discs` the step is hifigan_generator_step.
+    -> dict(gen_mel, gen_adv, gen_fm, gen_total, gen_grad_norm, disc_real, disc_fake, disc_total, disc_grad_norm)."""
+    from .hifigan_disc import hifigan_adversarial_losses, hifigan_discriminator_losses
+    y = batch['y']
+    gparams = [p for p in gen.parameters() if p.requires_grad]
+    dparams = [p for d in discs for p in d.parameters() if p.requires_grad]
+    for p in gparams + dparams:
+        p.grad = None
+    losses, y_hat = hifigan_generator_losses(gen, mel_loss, batch['x'], batch.get('f0'), y, lambda_mel=hp['lambda_mel'],
+                                             rand_ini=batch.get('rand_ini'), noise=batch.get('noise'))
+    y3 = y if y.dim() == 3 else y.unsqueeze(1)
+    total = losses['total']
+    for n, d in enumerate(discs):
+        terms = hifigan_adversarial_losses(d, y3, y_hat)
+        losses['adv'] = terms['adv'] if n == 0 else losses['adv'] + terms['adv']
+        losses['fm'] = terms['fm'] if n == 0 else losses['fm'] + terms['fm']
+        total = total + (terms['adv'] + terms['fm'])
+    losses['total'] = total
+    total.backward()
+    out = {'gen_' + k: v.detach() for k, v in losses.items()}
+    out['gen_grad_norm'] = _clip_and_step(gparams, hp.get('generator_grad_norm'), opt_g)
+    if discs:
+        for p in dparams:                                       # the generator's adversarial and feature terms left gradients here
+            p.grad = None
+        dl = None
+        for d in discs:
+            real, fake = hifigan_discriminator_losses(d, y3, y_hat)
+            dl = {'real': real, 'fake': fake} if dl is None else {'real': dl['real'] + real, 'fake': dl['fake'] + fake}
+        dl['total'] = dl['real'] + dl['fake']
+        dl['total'].backward()
+        out.update({'disc_' + k: v.detach() for k, v in dl.items()})
+        out['disc_grad_norm'] = _clip_and_step(dparams, hp.get('discriminator_grad_norm'), opt_d)
     return out

@@ -9,7 +9,9 @@ the trainer's two objectives as thin compositions of the operators that already 
 
 The reference's tasks.vocoder.pwg.PwgTask is missing from the snapshot this package was written against: the composition here
 is what the keys of configs/tts/pwg.yaml (stft_loss_params, lambda_adv, generator_grad_norm, discriminator_grad_norm, disc_start_steps) and the
-LSGAN losses of modules/hifigan/hifigan.py:337-365 define.  The optimiser is the caller's (optimizers/radam.py is not part of this package).
+LSGAN losses of modules/hifigan/hifigan.py:337-365 define.  The optimisers are arguments: voc_optim.pwg_optimizers builds the RAdam + StepLR
+pairs the same file configures (optimizers/radam.py's arithmetic on HIP over the list of parameter tensors), and a step given one of those
+clips and updates without reading the norm on the host; any other torch optimiser takes clip_grad_norm_ + step().
 
 Saved state of one forward: per block its input x_l [B][64][LS] and the gate pre-activations a_l [B][128][LS] (the backward recomputes tanh,
 sigmoid and z from a_l), the scaled skip sum, the hidden activation of last_conv_layers, the upsampled conditioning and each upsampling
@@ -25,6 +27,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from .pwg_disc import discriminator_loss, generator_loss
 from .vocoder import padded_samples
+from .voc_optim import MultiTensorOptimizer
 
 __all__ = ['pwg_gen_op', 'pwg_generator_losses', 'pwg_discriminator_losses', 'pwg_training_step', 'launch_count']
 
@@ -249,12 +252,24 @@ def pwg_discriminator_losses(disc, y, y_):
     return {'real': real, 'fake': fake, 'total': real + fake}
 
 
+def _clip_and_step(params, max_norm, opt):
+    """clip_grad_norm_(params, max_norm) and opt.step() when an optimiser is given -> the norm before clipping.  A MultiTensorOptimizer does
+    both itself, over ITS parameters (the trainer builds it on `params`)."""
+    if isinstance(opt, MultiTensorOptimizer):
+        return opt.clip_and_step(max_norm)
+    norm = torch.nn.utils.clip_grad_norm_(params, max_norm)
+    if opt is not None:
+        opt.step()
+    return norm
+
+
 def pwg_training_step(gen, disc, stft, batch, hp, global_step, opt_g=None, opt_d=None):
     """One step of the ParallelWaveGAN trainer as configs/tts/pwg.yaml defines it.  batch = dict(x noise [B][1][T], c padded mel, y target
     [B][1][T]); hp holds lambda_adv, generator_grad_norm, discriminator_grad_norm, disc_start_steps.  The generator objective (adversarial from
     disc_start_steps on) and its backward, clip_grad_norm_ at generator_grad_norm, opt_g.step() when given; from disc_start_steps on the
-    discriminator objective on the detached waveform, its backward, the clip at discriminator_grad_norm and opt_d.step().  Gradients are
-    zeroed here before each backward (set_to_none).  -> dict of the loss terms plus the two pre-clip gradient norms."""
+    discriminator objective on the detached waveform, its backward, the clip at discriminator_grad_norm and opt_d.step().  An optimiser that
+    is a voc_optim.MultiTensorOptimizer does clip and step in one go (clip_and_step: no host synchronisation; .grad stays unscaled).  Gradients
+    are zeroed here before each backward (set_to_none).  -> dict of the loss terms plus the two pre-clip gradient norms."""
     adversarial = global_step >= hp['disc_start_steps']
     x, c, y = batch['x'], batch['c'], batch['y']
     gparams = [p for p in gen.parameters() if p.requires_grad]
@@ -264,16 +279,12 @@ def pwg_training_step(gen, disc, stft, batch, hp, global_step, opt_g=None, opt_d
     losses, y_ = pwg_generator_losses(gen, disc, stft, x, c, y, lambda_adv=hp['lambda_adv'], adversarial=adversarial)
     losses['total'].backward()
     out = {'gen_' + k: v.detach() for k, v in losses.items()}
-    out['gen_grad_norm'] = torch.nn.utils.clip_grad_norm_(gparams, hp['generator_grad_norm'])
-    if opt_g is not None:
-        opt_g.step()
+    out['gen_grad_norm'] = _clip_and_step(gparams, hp['generator_grad_norm'], opt_g)
     if adversarial:
         for p in dparams:                                       # the generator's adversarial term left gradients here
             p.grad = None
         dl = pwg_discriminator_losses(disc, y, y_)
         dl['total'].backward()
         out.update({'disc_' + k: v.detach() for k, v in dl.items()})
-        out['disc_grad_norm'] = torch.nn.utils.clip_grad_norm_(dparams, hp['discriminator_grad_norm'])
-        if opt_d is not None:
-            opt_d.step()
+        out['disc_grad_norm'] = _clip_and_step(dparams, hp['discriminator_grad_norm'], opt_d)
     return out

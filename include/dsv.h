@@ -515,6 +515,38 @@ int dsv_hgp_l1_partial(const float* r, const float* g, void* workspace, int64_t 
 int dsv_hgp_l1_final(const void* workspace, int32_t nblocks, float* out, void* stream);
 int dsv_hgp_l1_backward(const float* r, const float* g, const float* grad_out, float* dr, float* dg, int64_t n, void* stream);
 
+/* Vocoder optimisers: RAdam (modules/parallel_wavegan/optimizers/radam.py:57-89, the optimiser configs/tts/pwg.yaml configures) and AdamW
+ * (torch.optim.AdamW; HiFi-GAN's adam_b1 / adam_b2) over a LIST of float32 tensors as they lie in memory, and the global L2 norm of a list of
+ * gradients with clip_grad_norm_'s coefficient - csrc/voc_optim.hpp.  p, g, m, v, n are HOST arrays of `count` device pointers / element
+ * counts; they are read before the call returns and need not outlive it (the tables travel in the kernel arguments: no copy to the device).
+ * Any float-aligned pointer, any n[i] in [1, 2^40]; the float4 path is taken where all pointers of a tensor are 16-byte aligned.  A list longer
+ * than the tables (dsv_mt_table_tensors() tensors, dsv_mt_table_chunks() chunks of dsv_mt_chunk_floats() floats per launch) is split over
+ * launches.  No atomics, a fixed order of additions: two calls are bitwise equal.  Nothing allocates, synchronises or reads a device value on
+ * the host; everything is enqueued on `stream`; bad arguments are refused with DSD_ERR_INVALID before any launch.
+ * dsv_mt_grad_norm: out2[0] = ||g||_2 over the whole list, out2[1] = min(1, max_norm / (out2[0] + 1e-6)) in float32 (max_norm >= 0, +inf: 1);
+ *   a non-finite norm propagates (NaN -> NaN, inf -> 0) as in torch.  workspace: dsv_mt_workspace_floats(n, count) floats, 8-byte aligned (one
+ *   float64 partial per chunk at the chunk's index in the whole list; one workgroup adds them in ascending order): the result does not depend
+ *   on how the list was split over launches.  dsv_mt_workspace_floats is host-only; -1 for a bad list.
+ * dsv_mt_radam_step: with g' = g * gscale[0] when gscale (a DEVICE scalar) is not NULL: v = v b2 + ((1 - b2) g') g'; m = m b1 + (1 - b1) g';
+ *   p += (-wd lr) p when wd != 0; p += ((-step_size lr) m) / (sqrt(v) + eps) when N_sma >= 5, p += (-step_size lr) m otherwise.  `step` >= 1 is the
+ *   count AFTER this update.  dsv_radam_scalars (host-only): out3 = {N_sma, step_size, 1.0 when N_sma >= 5 else 0.0}, formed in double as
+ *   radam.py:66-76 does.
+ * dsv_mt_adamw_step: dsf_adamw_step's arithmetic (include/dsf.h) on every tensor of the list.
+ * dsv_mt_set_table_limit(tensors, chunks): use fewer table entries per launch than the kernels hold (0: all of them) - process-wide, for tests
+ *   that cross the launch seam at small sizes. */
+int32_t dsv_mt_chunk_floats(void);
+int32_t dsv_mt_table_tensors(void);
+int32_t dsv_mt_table_chunks(void);
+int dsv_mt_set_table_limit(int32_t tensors, int32_t chunks);
+int64_t dsv_mt_workspace_floats(const int64_t* n, int64_t count);
+int dsv_mt_grad_norm(const float* const* g, const int64_t* n, int64_t count, double max_norm, float* workspace, int64_t workspace_floats, float* out2,
+                     void* stream);
+int dsv_radam_scalars(int64_t step, double beta1, double beta2, double* out3);
+int dsv_mt_radam_step(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n, int64_t count, double lr,
+                      double beta1, double beta2, double eps, double weight_decay, int64_t step, const float* gscale, void* stream);
+int dsv_mt_adamw_step(float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* n, int64_t count, double lr,
+                      double beta1, double beta2, double eps, double weight_decay, int64_t step, const float* gscale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
