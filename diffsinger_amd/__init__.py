@@ -23,6 +23,10 @@ Public surface mirrors the reference's own plugin API for this path:
                                         the multi-period discriminator (modules/hifigan/hifigan.py:181-250), forward and backward on HIP, the
                                         feature-matching loss (:328-334) and the generator's / discriminator's terms against it
                                         (diffsinger_amd/hifigan_disc.py)
+    DiscriminatorS, MultiScaleDiscriminator, disc_s_op
+                                        the multi-scale discriminator (modules/hifigan/hifigan.py:253-325): the grouped strided Conv1d stack
+                                        forward and backward on HIP, spectral and weight norm as torch expressions, the reference's state dict
+                                        (diffsinger_amd/hifigan_disc.py)
     HifiGanMelLoss, mel_spectrogram_loss_op, spec_logmel_op
                                         the mel-spectrogram loss of the HiFi-GAN trainer (modules/hifigan/mel_utils.py:45-76, lambda_mel) on
                                         the differentiable log-mel (diffsinger_amd/mel_loss.py, diffsinger_amd/stft.py)
@@ -49,6 +53,7 @@ __all__ = ['DIFF_DECODERS', 'DiffNet', 'GaussianDiffusion', 'OfflineGaussianDiff
            'pwg_gen_op', 'pwg_generator_losses', 'pwg_discriminator_losses', 'pwg_training_step',
            'avg_pool_op', 'cond_discriminator_loss',
            'DiscriminatorP', 'MultiPeriodDiscriminator', 'disc_p_op', 'feature_loss', 'hifigan_adversarial_losses', 'hifigan_discriminator_losses',
+           'DiscriminatorS', 'MultiScaleDiscriminator', 'disc_s_op',
            'pe_losses', 'pe_training_step',
            'HifiGanMelLoss', 'mel_spectrogram_loss_op', 'spec_logmel_op', 'hifigan_generator_losses', 'hifigan_generator_step',
            'hifigan_training_step', 'MultiTensorOptimizer', 'RAdam', 'AdamW', 'pwg_optimizers']
@@ -74,7 +79,7 @@ def __getattr__(name):      # lazy: torch-heavy modules load on first use
         from . import pwg_train
         return getattr(pwg_train, name)
     if name in ('avg_pool_op', 'cond_discriminator_loss', 'DiscriminatorP', 'MultiPeriodDiscriminator', 'disc_p_op', 'feature_loss',
-                'hifigan_adversarial_losses', 'hifigan_discriminator_losses'):
+                'hifigan_adversarial_losses', 'hifigan_discriminator_losses', 'DiscriminatorS', 'MultiScaleDiscriminator', 'disc_s_op'):
         from . import hifigan_disc
         return getattr(hifigan_disc, name)
     if name in ('pe_losses', 'pe_training_step'):

@@ -55,6 +55,8 @@ SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'ds
                'dsv_hgp_first_backward', 'dsv_hgp_post', 'dsv_hgp_post_backward', 'dsv_hgp_dgrad_phase_taps', 'dsv_hgp_dgrad_packed_offset', 'dsv_hgp_conv',
                'dsv_hgp_conv_dgrad', 'dsv_hgp_wgrad_splits', 'dsv_hgp_wgrad_workspace_floats', 'dsv_hgp_conv_wgrad', 'dsv_hgp_l1_blocks',
                'dsv_hgp_l1_partial', 'dsv_hgp_l1_final', 'dsv_hgp_l1_backward',
+               'dsv_hgs_out_len', 'dsv_hgs_first_workspace_floats', 'dsv_hgs_first', 'dsv_hgs_first_backward', 'dsv_hgs_packed_floats', 'dsv_hgs_pack',
+               'dsv_hgs_gconv', 'dsv_hgs_gconv_dgrad', 'dsv_hgs_wgrad_splits', 'dsv_hgs_wgrad_workspace_floats', 'dsv_hgs_gconv_wgrad',
                'dsv_mt_chunk_floats', 'dsv_mt_table_tensors', 'dsv_mt_table_chunks', 'dsv_mt_set_table_limit', 'dsv_mt_workspace_floats', 'dsv_mt_grad_norm',
                'dsv_radam_scalars', 'dsv_mt_radam_step', 'dsv_mt_adamw_step']
 
@@ -344,6 +346,22 @@ def load():
     lib.dsv_hgp_l1_partial.argtypes = [vp, vp, vp, i64, vp]
     lib.dsv_hgp_l1_final.argtypes = [vp, i32, vp, vp]
     lib.dsv_hgp_l1_backward.argtypes = [vp, vp, vp, vp, vp, i64, vp]
+    lib.dsv_hgs_out_len.argtypes = [i32, i32]
+    lib.dsv_hgs_out_len.restype = i32
+    lib.dsv_hgs_first_workspace_floats.argtypes = [i32, i32, i32]
+    lib.dsv_hgs_first_workspace_floats.restype = i64
+    lib.dsv_hgs_first.argtypes = [vp, vp, vp, vp, i32, i32, i32, i64, f32, vp]
+    lib.dsv_hgs_first_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, vp]
+    lib.dsv_hgs_packed_floats.argtypes = [i32, i32, i32, i32, i32]
+    lib.dsv_hgs_packed_floats.restype = i64
+    lib.dsv_hgs_pack.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+    lib.dsv_hgs_gconv.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]
+    lib.dsv_hgs_gconv_dgrad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]
+    lib.dsv_hgs_wgrad_splits.argtypes = [i32, i32, i32, i32, i32, i32]
+    lib.dsv_hgs_wgrad_splits.restype = i32
+    lib.dsv_hgs_wgrad_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32]
+    lib.dsv_hgs_wgrad_workspace_floats.restype = i64
+    lib.dsv_hgs_gconv_wgrad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     f64 = C.c_double
     for name in ('dsv_mt_chunk_floats', 'dsv_mt_table_tensors', 'dsv_mt_table_chunks'):
         getattr(lib, name).argtypes = []

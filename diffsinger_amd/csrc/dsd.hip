@@ -1449,5 +1449,6 @@ extern "C" int dsd_debug_layer_timeline(dsd_handle* h, int32_t layer, int32_t t,
 #include "hifigan_train_abi.hpp"
 #include "hifigan_disc.hpp"
 #include "hifigan_mpd_abi.hpp"
+#include "hifigan_msd_abi.hpp"
 #include "pe_train.hpp"
 #include "voc_optim_abi.hpp"

@@ -1,5 +1,5 @@
-"""HiFi-GAN discriminators on the HIP operators of include/dsv.h, sections "HiFi-GAN scale discriminator" (kernels: csrc/hifigan_disc.hpp) and
-"HiFi-GAN period discriminator" (csrc/hifigan_mpd.hpp).
+"""HiFi-GAN discriminators on the HIP operators of include/dsv.h, sections "HiFi-GAN scale discriminator" (kernels: csrc/hifigan_disc.hpp),
+"HiFi-GAN scale discriminator stack" (csrc/hifigan_msd.hpp) and "HiFi-GAN period discriminator" (csrc/hifigan_mpd.hpp).
 
     avg_pool_op                                AvgPool1d(4, 2, padding=1) of MultiScaleDiscriminator (modules/hifigan/hifigan.py:304-307), forward
                                                and backward
@@ -7,11 +7,16 @@
     disc_p_op                                  DiscriminatorP (hifigan.py:181-227) on plain weights, forward and backward through ONE autograd node
     feature_loss                               hifigan.py:328-334
     DiscriminatorP, MultiPeriodDiscriminator   hifigan.py:181-250: the reference's constructor signatures and state-dict keys
+    disc_s_op                                  DiscriminatorS (hifigan.py:253-286) on plain weights - the grouped, strided Conv1d stack - forward and
+                                               backward through ONE autograd node
+    DiscriminatorS, MultiScaleDiscriminator    hifigan.py:253-325: the reference's constructor signatures and state-dict keys; spectral norm (with its
+                                               power iteration in train()) and weight norm are torch expressions
     hifigan_adversarial_losses, hifigan_discriminator_losses       the generator's adversarial + feature-matching terms, the discriminator's pair
 
-DiscriminatorS itself - the grouped, strided Conv1d stack - is not here: see DESIGN.md section 6 "HiFi-GAN scale discriminator".  There is no CPU
-path.  Nothing here synchronises or reads a device value on the host, every launch goes to the current stream and the library allocates nothing;
-recording these operators into a torch.cuda.graph is UNVERIFIED (no test or tool does it).
+There is no CPU path.  Nothing here synchronises or reads a device value on the host, every launch goes to the current stream and the library
+allocates nothing; recording these operators - the period discriminator's and the scale discriminator's alike - into a captured graph is UNVERIFIED
+and UNSUPPORTED (no test or tool does it), and the capture fault of an earlier, unpublished version of the scale discriminator's kernels (DESIGN.md
+section 6 "HiFi-GAN scale discriminator") is still unexplained: whoever records these operators into a graph has to explain it first.
 
 The period discriminator's activations are the reference's tensors, dense [B][C][H][p]: the feature maps disc_p_op returns are views of the buffers
 its kernels wrote, and the module runs d(y) and d(y_hat) as ONE batch of 2 B - every layer's weights stream once per pass - and hands out the two
@@ -24,13 +29,22 @@ and one backward; lsgan_loss_op 2 forward, 1 backward.  disc_p_op forward is 15:
 kernel and slack fill, the convolution), conv_post 1.  Its backward is 37 + s + 2 x: conv_post 3 (parameter gradients, their reduction, data
 gradient), per dense layer 1 weight gradient + 1 bias gradient (+ 1 reduction where dsv_hgp_wgrad_splits > 1: s counts those layers), its
 data gradient 2 r + 1 (r = stride: one pack per input phase; 7, 7, 7, 3), the first layer 2, and x = 1 when the input requires a gradient: 2
-more (first layer's data gradient, the fold's adjoint); a layer without a bias is one less.  feature_loss over n pairs is n + 1 forward, n backward."""
+more (first layer's data gradient, the fold's adjoint); a layer without a bias is one less.  feature_loss over n pairs is n + 1 forward, n backward.
+
+The scale discriminator's activations are dense [B][C][L] and the same rules hold: the maps disc_s_op returns are views of its buffers, the module
+runs d(y) and d(y_hat) as one batch of 2 B (pooled as one batch, too) wherever the weights are the same for both - the weight-normed
+discriminators always, the spectral-normed one in eval(); in train() its buffers move between the two calls, so it runs twice, y first.
+disc_s_op forward is 15 launches: first layer 1, per grouped layer 2 (dsv_hgs_pack, dsv_hgs_gconv), the dense layer 3 (dsv_pack_weight's two, dsv_hgp_conv
+at period 1), conv_post 1 (dsv_hgp_post).  Its backward is 30 + s + x: conv_post 3, the dense layer 5 (weight gradient, bias gradient, the pack's
+two, data gradient), per grouped layer 4 (weight gradient, bias gradient, dsv_hgs_pack of the phase matrices, data gradient; + 1 reduction where
+dsv_hgs_wgrad_splits > 1: s counts those layers), the first layer 2 and x = 1 when the input requires a gradient; a layer without a bias is one less."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _lib
@@ -39,7 +53,8 @@ from .pwg_disc import _call, _check_x as _check_pwg_x, discriminator_loss, gener
 from .vocoder import padded_samples
 
 __all__ = ['avg_pool_op', 'generator_loss', 'discriminator_loss', 'cond_discriminator_loss', 'launch_count', 'disc_p_op', 'feature_loss',
-           'DiscriminatorP', 'MultiPeriodDiscriminator', 'hifigan_adversarial_losses', 'hifigan_discriminator_losses', 'period_heights']
+           'DiscriminatorP', 'MultiPeriodDiscriminator', 'hifigan_adversarial_losses', 'hifigan_discriminator_losses', 'period_heights',
+           'disc_s_op', 'DiscriminatorS', 'MultiScaleDiscriminator', 'scale_lengths']
 
 
 def _check_x(x, who, min_t=1):
@@ -404,14 +419,322 @@ class MultiPeriodDiscriminator(nn.Module):
         return rs, gs, frs, fgs
 
 
+# ---- the scale discriminator ------------------------------------------------------------------------------------------------------------------
+# (Ci, Co, K, stride, groups), padding (K - 1) / 2: hifigan.py:263-271; conv_post 1024 -> 1
+_S_LAYERS = ((1, 128, 15, 1, 1), (128, 128, 41, 2, 4), (128, 256, 41, 2, 16), (256, 512, 41, 4, 16), (512, 1024, 41, 4, 16), (1024, 1024, 41, 1, 16),
+             (1024, 1024, 5, 1, 1), (1024, 1, 3, 1, 1))
+_SN_LAYERS = len(_S_LAYERS)
+
+
+def scale_lengths(T: int):
+    """[L_0 .. L_7]: the output length of every layer of DiscriminatorS for T samples, (L - 1) // stride + 1"""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f'scale_lengths: T={T} must be >= 1')
+    out = []
+    for _, _, _, s, _ in _S_LAYERS:
+        T = (T - 1) // s + 1
+        out.append(T)
+    return out
+
+
+class DiscSFunction(torch.autograd.Function):
+    """x [B][1][T] (rows ld >= T floats apart), eight weights [Co][Ci / g][K], eight biases (None where absent) -> (out [B][L_7], a_0 .. a_6, a_7 =
+    conv_post's output [B][1][L_7]): views of the node's buffers.  pair=True: B = 2 Bh and every output is handed out as its two halves, (out_r,
+    out_g, the eight maps' first halves, the eight second halves)."""
+
+    @staticmethod
+    def forward(ctx, x, slope, pair, *params):
+        lib = _lib.load()
+        n = _SN_LAYERS
+        ws, bs = params[:n], params[n:]
+        dev = x.device
+        B, _, T = x.shape
+        ld = x.stride(0) if B > 1 else T
+        ls = scale_lengths(T)
+        wd = [w.detach().contiguous() for w in ws]
+        b = [None if t is None else t.detach().contiguous() for t in bs]
+        acts = [torch.empty(B, _S_LAYERS[l][1], ls[l], device=dev, dtype=torch.float32) for l in range(n - 1)]
+        _call('dsv_hgs_first', 1, dev, x.data_ptr(), wd[0].data_ptr(), _lib.ptr(b[0]), acts[0].data_ptr(), B, _S_LAYERS[0][1], T, ld, slope)
+        for l in range(1, 6):
+            ci, co, _, s, g = _S_LAYERS[l]
+            packed = torch.empty(lib.dsv_hgs_packed_floats(ci, co, s, g, 0), device=dev, dtype=torch.float32)
+            _call('dsv_hgs_pack', 1, dev, wd[l].data_ptr(), packed.data_ptr(), ci, co, s, g, 0)
+            _call('dsv_hgs_gconv', 1, dev, acts[l - 1].data_ptr(), packed.data_ptr(), _lib.ptr(b[l]), acts[l].data_ptr(), B, ci, co, ls[l - 1], s, g, slope)
+        ci, co, k = _S_LAYERS[6][:3]
+        packed = torch.empty(lib.dsv_packed_floats(co, ci, k), device=dev, dtype=torch.float32)
+        _call('dsv_pack_weight', 2, dev, wd[6].data_ptr(), co, ci, k, packed.data_ptr())
+        _call('dsv_hgp_conv', 1, dev, acts[5].data_ptr(), packed.data_ptr(), _lib.ptr(b[6]), acts[6].data_ptr(), B, ci, co, ls[5], 1, 1, slope)
+        post = torch.empty(B, 1, ls[7], device=dev, dtype=torch.float32)
+        _call('dsv_hgp_post', 1, dev, acts[6].data_ptr(), wd[7].data_ptr(), _lib.ptr(b[7]), post.data_ptr(), B, _S_LAYERS[7][0], ls[7], 1)
+        ctx.save_for_backward(x, *wd, *acts)
+        ctx.meta = (B, T, ld, float(slope), bool(pair), ls, [t is not None for t in bs])
+        out = post.view(B, ls[7])
+        maps = acts + [post]
+        if not pair:
+            return (out,) + tuple(maps)
+        Bh = B // 2
+        return (out[:Bh], out[Bh:]) + tuple(m[:Bh] for m in maps) + tuple(m[Bh:] for m in maps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *cots):
+        lib = _lib.load()
+        n = _SN_LAYERS
+        x, *rest = ctx.saved_tensors
+        wd, acts = rest[:n], rest[n:]
+        B, T, ld, slope, pair, ls, has_b = ctx.meta
+        dev = x.device
+        keep = []                                               # tensors whose addresses are in flight
+        if pair:
+            g_out, k = _join(cots[0], cots[1], (B, ls[7]), dev)
+            keep.append(k)
+            cot = []
+            for l in range(n):
+                a, k = _join(cots[2 + l], cots[2 + n + l], (B, _S_LAYERS[l][1], ls[l]), dev)
+                cot.append(a); keep.append(k)
+        else:
+            t = _f32c(cots[0])
+            g_out = None if t is None else t.data_ptr()
+            keep.append(t)
+            cot = []
+            for l in range(n):
+                t = _f32c(cots[1 + l])
+                cot.append(None if t is None else t.data_ptr()); keep.append(t)
+        gp1, gp2 = (g_out, cot[7]) if g_out is not None else (cot[7], None)
+        if gp1 is None:                                         # nothing arrives on the output: its cotangent is zero
+            z = torch.zeros(B, ls[7], device=dev, dtype=torch.float32)
+            keep.append(z)
+            gp1 = z.data_ptr()
+        dws: List[Optional[torch.Tensor]] = [None] * n
+        dbs: List[Optional[torch.Tensor]] = [None] * n
+
+        def grads(l):
+            ci, co, k, _, g = _S_LAYERS[l]
+            dws[l] = torch.empty(co, ci // g, k, device=dev, dtype=torch.float32)
+            dbs[l] = torch.empty(co, device=dev, dtype=torch.float32) if has_b[l] else None
+
+        grads(7)
+        C = _S_LAYERS[7][0]
+        ws_e = torch.empty(lib.dsv_hgp_edge_workspace_floats(B, ls[7], 1, C, _KPOST), device=dev, dtype=torch.float32)
+        G = torch.empty(B, C, ls[6], device=dev, dtype=torch.float32)
+        _call('dsv_hgp_post_backward', 3, dev, gp1, gp2, acts[6].data_ptr(), wd[7].data_ptr(), cot[6], ws_e.data_ptr(), dws[7].data_ptr(), _lib.ptr(dbs[7]),
+              G.data_ptr(), B, C, ls[7], 1, slope)
+        # the dense 1024 -> 1024 layer: the period discriminator's fifth layer at period 1
+        grads(6)
+        ci, co, k = _S_LAYERS[6][:3]
+        nws = lib.dsv_hgp_wgrad_workspace_floats(B, ci, co, ls[6], 1)
+        ws_w = torch.empty(nws, device=dev, dtype=torch.float32) if nws else None
+        _call('dsv_hgp_conv_wgrad', 1 + (1 if nws else 0) + (1 if has_b[6] else 0), dev, G.data_ptr(), acts[5].data_ptr(), _lib.ptr(ws_w), dws[6].data_ptr(),
+              _lib.ptr(dbs[6]), B, ci, co, ls[5], 1, 1)
+        packed = torch.empty(lib.dsv_hgp_dgrad_packed_offset(ci, co, 1, 1), device=dev, dtype=torch.float32)
+        m = wd[6].permute(1, 0, 2).contiguous()                 # [ci][co][k]
+        _call('dsv_pack_weight', 2, dev, m.data_ptr(), ci, co, k, packed.data_ptr())
+        Gn = torch.empty(B, ci, ls[5], device=dev, dtype=torch.float32)
+        _call('dsv_hgp_conv_dgrad', 1, dev, G.data_ptr(), packed.data_ptr(), cot[5], acts[5].data_ptr(), Gn.data_ptr(), B, ci, co, ls[5], 1, 1, slope)
+        G = Gn
+        for l in range(5, 0, -1):
+            ci, co, _, s, g = _S_LAYERS[l]
+            grads(l)
+            nws = lib.dsv_hgs_wgrad_workspace_floats(B, ci, co, ls[l], s, g)
+            ws_w = torch.empty(nws, device=dev, dtype=torch.float32) if nws else None
+            _call('dsv_hgs_gconv_wgrad', 1 + (1 if nws else 0) + (1 if has_b[l] else 0), dev, G.data_ptr(), acts[l - 1].data_ptr(), _lib.ptr(ws_w),
+                  dws[l].data_ptr(), _lib.ptr(dbs[l]), B, ci, co, ls[l - 1], s, g)
+            packed = torch.empty(lib.dsv_hgs_packed_floats(ci, co, s, g, 1), device=dev, dtype=torch.float32)
+            _call('dsv_hgs_pack', 1, dev, wd[l].data_ptr(), packed.data_ptr(), ci, co, s, g, 1)
+            Gn = torch.empty(B, ci, ls[l - 1], device=dev, dtype=torch.float32)
+            _call('dsv_hgs_gconv_dgrad', 1, dev, G.data_ptr(), packed.data_ptr(), cot[l - 1], acts[l - 1].data_ptr(), Gn.data_ptr(), B, ci, co, ls[l - 1], s, g,
+                  slope)
+            G = Gn
+        grads(0)
+        C = _S_LAYERS[0][1]
+        need_dx = ctx.needs_input_grad[0]
+        ws_f = torch.empty(lib.dsv_hgs_first_workspace_floats(B, T, C), device=dev, dtype=torch.float32)
+        dx = torch.empty(B, T, device=dev, dtype=torch.float32) if need_dx else None
+        _call('dsv_hgs_first_backward', 3 if need_dx else 2, dev, G.data_ptr(), x.data_ptr(), wd[0].data_ptr(), ws_f.data_ptr(), dws[0].data_ptr(),
+              _lib.ptr(dbs[0]), _lib.ptr(dx), B, C, T, ld)
+        del keep
+        return (None if dx is None else dx[:, None, :], None, None) + tuple(dws) + tuple(dbs)
+
+
+def _check_sx(x, who, min_t=1):
+    _check_x(x, who, min_t)
+    if x.shape[2] > 1 << 30:
+        raise ValueError(f'{who}: x has T={x.shape[2]} > 2^30 samples')
+
+
+def _check_s_params(x, weights, biases, slope, who):
+    if len(weights) != _SN_LAYERS or len(biases) != _SN_LAYERS:
+        raise ValueError(f'{who}: eight weights and eight biases (None where absent), got {len(weights)} and {len(biases)}')
+    if not 0.0 < float(slope) < 1.0:
+        raise ValueError(f'{who}: slope={slope} must be in (0, 1)')
+    for i, w in enumerate(weights):
+        ci, co, k, _, g = _S_LAYERS[i]
+        want = (co, ci // g, k)
+        if not isinstance(w, torch.Tensor) or tuple(w.shape) != want or w.dtype != torch.float32 or w.device != x.device:
+            raise ValueError(f'{who}: weights[{i}] must be float32 {want} on {x.device}')
+        bi = biases[i]
+        if bi is not None and (not isinstance(bi, torch.Tensor) or tuple(bi.shape) != (co,) or bi.dtype != torch.float32 or bi.device != x.device):
+            what = f'{bi.dtype} {tuple(bi.shape)} on {bi.device}' if isinstance(bi, torch.Tensor) else type(bi).__name__
+            raise ValueError(f'{who}: biases[{i}] must be float32 ({co},) on {x.device}, got {what}')
+
+
+def _rows(x):
+    """x [B][1][T] as the kernels take it: rows of unit stride, at least T floats apart (avg_pool_op's view is one), else a dense copy"""
+    B, _, T = x.shape
+    if x.stride(2) == 1 and (B == 1 or x.stride(0) >= T) and x.stride(0) <= 1 << 31:
+        return x
+    return x.contiguous()
+
+
+def disc_s_op(x, weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]], slope: float = LRELU_SLOPE):
+    """DiscriminatorS.forward on plain weights: weights[l] [Co][Ci / groups][K] for the seven convs (1 -> 128 K 15; 128 -> 128, 128 -> 256, 256 -> 512,
+    512 -> 1024, 1024 -> 1024 at K 41, stride 2, 2, 4, 4, 1, groups 4, 16, 16, 16, 16; 1024 -> 1024 K 5), weights[7] [1][1024][3]; biases[l] [Co] or
+    None; x float32 [B][1][T] on the device -> (out [B][L_7], fmap): the eight feature maps [B][C][L_l], views of the node's own buffers (fmap[7]
+    and out are the same values).  Differentiable with respect to x, every weight and every bias; cotangents are accepted on out and on every map."""
+    _check_sx(x, 'disc_s_op')
+    _check_s_params(x, weights, biases, slope, 'disc_s_op')
+    res = DiscSFunction.apply(_rows(x), float(slope), False, *weights, *biases)
+    return res[0], list(res[1:])
+
+
+def _disc_s_pair(yy, weights, biases, slope):
+    """disc_s_op over cat(y, y_hat): ((out_r, fmap_r), (out_g, fmap_g)), every tensor a half of the node's buffers"""
+    res = DiscSFunction.apply(_rows(yy), float(slope), True, *weights, *biases)
+    n = _SN_LAYERS
+    return (res[0], list(res[2:2 + n])), (res[1], list(res[2 + n:]))
+
+
+class _SN(nn.Module):
+    """spectral_norm(Conv1d) parameter holder with torch.nn.utils.spectral_norm's state-dict keys - bias, weight_orig, buffers weight_u [Co] and
+    weight_v [Ci / g K] - and its semantics: in train() every weight() call does one power iteration on the buffers under no_grad (v =
+    normalize(W^T u), u = normalize(W v), in place), then sigma = u . (W v) with u and v constant and weight = W / sigma; in eval() no iteration."""
+
+    def __init__(self, wshape, eps=1e-12):
+        super().__init__()
+        self.eps = eps
+        self.bias = nn.Parameter(torch.zeros(wshape[0]))
+        w = torch.randn(wshape) * 0.01
+        self.weight_orig = nn.Parameter(w)
+        W = w.flatten(1)
+        self.register_buffer('weight_u', F.normalize(torch.randn(W.shape[0]), dim=0, eps=eps))
+        self.register_buffer('weight_v', F.normalize(torch.randn(W.shape[1]), dim=0, eps=eps))
+
+    def weight(self):
+        W = self.weight_orig.flatten(1)
+        u, v = self.weight_u, self.weight_v
+        if self.training:
+            with torch.no_grad():
+                v = F.normalize(torch.mv(W.t(), u), dim=0, eps=self.eps, out=v)
+                u = F.normalize(torch.mv(W, v), dim=0, eps=self.eps, out=u)
+            u, v = u.clone(memory_format=torch.contiguous_format), v.clone(memory_format=torch.contiguous_format)
+        sigma = torch.dot(u, torch.mv(W, v))
+        return self.weight_orig / sigma
+
+
+class DiscriminatorS(nn.Module):
+    """modules/hifigan/hifigan.py:253-286.  forward(x [B,1,T], mel=None) -> (out [B, L_7], fmap: eight maps [B, C, L_l]), differentiable with respect
+    to x and every parameter.  convs[l] / conv_post hold bias and weight_g [Co,1,1], weight_v [Co,Ci/g,K] (or weight after remove_weight_norm());
+    under use_spectral_norm weight_orig and the buffers weight_u, weight_v.  The normalisations are torch expressions."""
+
+    def __init__(self, use_spectral_norm=False, use_cond=False, upsample_rates=None, c_in=1):
+        super().__init__()
+        bad = []
+        if use_cond:
+            bad.append('use_cond (the mel-conditioned input)')
+        if c_in != 1:
+            bad.append('c_in other than 1')
+        if bad:
+            raise NotImplementedError('DiscriminatorS on HIP covers the shipped configuration only: ' + '; '.join(bad))
+        self.use_cond, self.use_spectral_norm = False, bool(use_spectral_norm)
+        shapes = [(co, ci // g, k) for ci, co, k, _, g in _S_LAYERS]
+        mods = [_SN(s) if use_spectral_norm else _WN(s, True, True, bias_first=True) for s in shapes]
+        self.convs = nn.ModuleList(mods[:-1])
+        self.conv_post = mods[-1]
+
+    def remove_weight_norm(self):
+        for m in self.modules():
+            if isinstance(m, _WN):
+                m.remove_weight_norm()
+
+    def _params(self):
+        mods = list(self.convs) + [self.conv_post]
+        ws = [m.weight() if isinstance(m, _SN) else torch._weight_norm(m.weight_v, m.weight_g, 0) if hasattr(m, 'weight_g') else m.weight for m in mods]
+        return ws, [m.bias for m in mods]
+
+    def _check_device(self, x, who):
+        p = self.conv_post.bias
+        if p.device != x.device or p.dtype != torch.float32:
+            raise ValueError(f'{who}: the parameters are {p.dtype} on {p.device}, x is on {x.device}')
+
+    def forward(self, x, mel=None):
+        if mel is not None:
+            raise NotImplementedError('DiscriminatorS on HIP: use_cond (a mel input) is not supported')
+        _check_sx(x, 'DiscriminatorS')
+        self._check_device(x, 'DiscriminatorS')
+        ws, bs = self._params()
+        return disc_s_op(x, ws, bs, LRELU_SLOPE)
+
+
+class _MeanPool(nn.Module):
+    """AvgPool1d(4, 2, padding=1) on avg_pool_op: a parameter-free member, as the reference's meanpools are"""
+
+    def forward(self, x):
+        return avg_pool_op(x)
+
+
+class MultiScaleDiscriminator(nn.Module):
+    """modules/hifigan/hifigan.py:289-325: three DiscriminatorS, the first under spectral norm, behind cumulative AvgPool1d(4, 2, 1).  forward(y, y_hat,
+    mel=None) -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs); T >= 4.  The weight-normed discriminators run d(y) and d(y_hat) as one batch of 2 B; the
+    spectral-normed one too in eval(), but in train() as two calls, y first: its buffers move between them, as in the reference."""
+
+    def __init__(self, use_cond=False, c_in=1):
+        super().__init__()
+        self.discriminators = nn.ModuleList([DiscriminatorS(use_spectral_norm=True, use_cond=use_cond, c_in=c_in),
+                                             DiscriminatorS(use_cond=use_cond, c_in=c_in), DiscriminatorS(use_cond=use_cond, c_in=c_in)])
+        self.meanpools = nn.ModuleList([_MeanPool(), _MeanPool()])
+
+    def remove_weight_norm(self):
+        for d in self.discriminators:
+            d.remove_weight_norm()
+
+    def forward(self, y, y_hat, mel=None):
+        if mel is not None:
+            raise NotImplementedError('MultiScaleDiscriminator on HIP: use_cond (a mel input) is not supported')
+        _check_sx(y, 'MultiScaleDiscriminator', 4)
+        _check_pwg_x(y_hat, 'MultiScaleDiscriminator')
+        if y_hat.shape != y.shape or y_hat.device != y.device:
+            raise ValueError(f'MultiScaleDiscriminator: y {tuple(y.shape)} on {y.device} against y_hat {tuple(y_hat.shape)} on {y_hat.device}')
+        if 2 * y.shape[0] > 65535:
+            raise ValueError(f'MultiScaleDiscriminator: 2 B = {2 * y.shape[0]} exceeds 65535 rows')
+        for d in self.discriminators:
+            d._check_device(y, 'MultiScaleDiscriminator')
+        yy = torch.cat([y, y_hat]).contiguous()
+        rs, gs, frs, fgs = [], [], [], []
+        for i, d in enumerate(self.discriminators):
+            if i != 0:
+                yy = self.meanpools[i - 1](yy)                  # the pooling is per row: the pair is pooled as one batch
+            if d.use_spectral_norm and self.training:
+                Bh = yy.shape[0] // 2
+                r, fr = d(yy[:Bh])
+                g, fg = d(yy[Bh:])
+            else:
+                ws, bs = d._params()
+                _check_s_params(yy, ws, bs, LRELU_SLOPE, 'MultiScaleDiscriminator')
+                (r, fr), (g, fg) = _disc_s_pair(yy, ws, bs, LRELU_SLOPE)
+            rs.append(r); gs.append(g); frs.append(fr); fgs.append(fg)
+        return rs, gs, frs, fgs
+
+
 def hifigan_adversarial_losses(disc, y, y_hat):
-    """the generator's terms against `disc` (a MultiPeriodDiscriminator): dict(adv = generator_loss(d(y_hat)), fm = feature_loss(fmaps of y, of
+    """the generator's terms against `disc` (a MultiPeriodDiscriminator or a MultiScaleDiscriminator): dict(adv = generator_loss(d(y_hat)), fm = feature_loss(fmaps of y, of
     y_hat)); gradients flow to y_hat (and to the discriminator's parameters, which a generator step does not update)"""
     _, gs, frs, fgs = disc(y, y_hat)
     return dict(adv=generator_loss(gs), fm=feature_loss(frs, fgs))
 
 
 def hifigan_discriminator_losses(disc, y, y_hat):
-    """the discriminator's pair (r_loss, g_loss) = discriminator_loss(d(y), d(y_hat.detach()))"""
+    """the discriminator's pair (r_loss, g_loss) = discriminator_loss(d(y), d(y_hat.detach())) of `disc` (a MultiPeriodDiscriminator or a
+    MultiScaleDiscriminator; the latter's spectral buffers advance once per d(.) call in train())"""
     rs, gs, _, _ = disc(y, y_hat.detach())
     return discriminator_loss(rs, gs)

@@ -29,16 +29,18 @@ class _WN(nn.Module):
     """weight_norm(Conv1d / Conv2d) parameter holder: weight_g / weight_v (/ bias) as a checkpoint stores them, or weight after
     remove_weight_norm() (torch.nn.utils.weight_norm, dim 0)."""
 
-    def __init__(self, wshape, bias: bool, weight_norm: bool):
+    def __init__(self, wshape, bias: bool, weight_norm: bool, bias_first: bool = False):
         super().__init__()
+        if bias and bias_first:                                 # torch's Conv1d registers its bias in front of what a norm adds: that key order
+            self.bias = nn.Parameter(torch.zeros(wshape[0]))
         if weight_norm:
             self.weight_g = nn.Parameter(torch.ones(wshape[0], *([1] * (len(wshape) - 1))))
             self.weight_v = nn.Parameter(torch.randn(wshape) * 0.01)
         else:
             self.weight = nn.Parameter(torch.randn(wshape) * 0.01)
-        if bias:
+        if bias and not bias_first:
             self.bias = nn.Parameter(torch.zeros(wshape[0]))
-        else:
+        elif not bias:
             self.bias = None
 
     def remove_weight_norm(self):

@@ -515,6 +515,45 @@ int dsv_hgp_l1_partial(const float* r, const float* g, void* workspace, int64_t 
 int dsv_hgp_l1_final(const void* workspace, int32_t nblocks, float* out, void* stream);
 int dsv_hgp_l1_backward(const float* r, const float* g, const float* grad_out, float* dr, float* dg, int64_t n, void* stream);
 
+/* HiFi-GAN scale discriminator stack: DiscriminatorS (modules/hifigan/hifigan.py:253-286) forward and backward - csrc/hifigan_msd.hpp.  Its dense
+ * 1024 -> 1024 (K 5) layer and conv_post are dsv_hgp_conv / _conv_dgrad / _conv_wgrad and dsv_hgp_post / _post_backward at period 1.  No atomics, a
+ * fixed order of additions (two calls are bitwise equal; a forward value and a data gradient do not depend on the batch they are computed in);
+ * nothing allocates, copies, synchronises or reads a device value on the host; everything is enqueued on `stream`; bad shapes, null pointers and
+ * overlapping input and output ranges are refused with DSD_ERR_INVALID before any launch.
+ * LAYOUT: every activation is the reference's tensor, dense [B][C][L] float32 - no padding, no tail; nothing outside it is read or written.
+ *   B in [1, 65535], L in [1, 2^30].  dsv_hgs_out_len(L, stride) = (L - 1) / stride + 1 (kernel 41, padding 20; stride 1, 2 or 4; -1 otherwise).
+ * dsv_hgs_first: x, B rows ld_x >= T floats apart (nothing is read beyond sample T of a row), w [C][15], bias [C] or NULL -> out =
+ *   leaky_relu(conv) [B][C][T] (padding 7).  dsv_hgs_first_backward: g0 [B][C][T] the gradient with respect to the pre-activation -> dw [C][15],
+ *   db [C] or NULL, dx [B][T] or NULL; float64 sums in a fixed order; workspace: dsv_hgs_first_workspace_floats(B, T, C) floats.
+ * The grouped layers: (Ci, Co, stride, groups) is one of (128, 128, 2, 4), (128, 256, 2, 16), (256, 512, 4, 16), (512, 1024, 4, 16),
+ *   (1024, 1024, 1, 16); anything else is refused.  Weights are [Co][Ci / groups][41].
+ * dsv_hgs_pack: w -> packed (16-byte aligned, dsv_hgs_packed_floats(Ci, Co, stride, groups, dgrad) floats): the MFMA operand stream of dsv_hgs_gconv
+ *   (dgrad = 0) or of dsv_hgs_gconv_dgrad (dgrad = 1: one matrix per input phase).
+ * dsv_hgs_gconv: x [B][Ci][L] -> out = leaky_relu(conv + bias) [B][Co][Lo], Lo = dsv_hgs_out_len(L, stride); bias [Co] or NULL.  fp32 MFMA, exact
+ *   fp32 products; the order of an output's sum is tap, then channel.
+ * dsv_hgs_gconv_dgrad: g [B][Co][Lo] -> out [B][Ci][L] = (W^T g + cot) * mask(saved), polyphase (input position stride m + r receives only the
+ *   taps k = (r + 20) mod stride, + stride, ..); cot (the cotangent arriving on the feature map below) and saved (that feature map: mask 1 where
+ *   > 0, else slope) may be NULL.
+ * dsv_hgs_gconv_wgrad: dw [Co][Ci / groups][41] = sum over (b, q) of g[b][co][q] x[b][ci][q stride + k - 20] on the MFMA, db [Co] (or NULL) = sum of
+ *   g in float64.  dsv_hgs_wgrad_splits(B, Ci, Co, Lo, stride, groups): splits of the position axis; workspace:
+ *   dsv_hgs_wgrad_workspace_floats(..) floats (0 for one split). */
+int32_t dsv_hgs_out_len(int32_t L, int32_t stride);
+int64_t dsv_hgs_first_workspace_floats(int32_t B, int32_t T, int32_t C);
+int dsv_hgs_first(const float* x, const float* w, const float* bias, float* out, int32_t B, int32_t C, int32_t T, int64_t ld_x, float slope,
+                  void* stream);
+int dsv_hgs_first_backward(const float* g0, const float* x, const float* w, float* workspace, float* dw, float* db, float* dx, int32_t B, int32_t C,
+                           int32_t T, int64_t ld_x, void* stream);
+int64_t dsv_hgs_packed_floats(int32_t Ci, int32_t Co, int32_t stride, int32_t groups, int32_t dgrad);
+int dsv_hgs_pack(const float* w, float* packed, int32_t Ci, int32_t Co, int32_t stride, int32_t groups, int32_t dgrad, void* stream);
+int dsv_hgs_gconv(const float* x, const float* w_packed, const float* bias, float* out, int32_t B, int32_t Ci, int32_t Co, int32_t L, int32_t stride,
+                  int32_t groups, float slope, void* stream);
+int dsv_hgs_gconv_dgrad(const float* g, const float* w_packed, const float* cot, const float* saved, float* out, int32_t B, int32_t Ci, int32_t Co,
+                        int32_t L, int32_t stride, int32_t groups, float slope, void* stream);
+int32_t dsv_hgs_wgrad_splits(int32_t B, int32_t Ci, int32_t Co, int32_t L_out, int32_t stride, int32_t groups);
+int64_t dsv_hgs_wgrad_workspace_floats(int32_t B, int32_t Ci, int32_t Co, int32_t L_out, int32_t stride, int32_t groups);
+int dsv_hgs_gconv_wgrad(const float* g, const float* x, float* workspace, float* dw, float* db, int32_t B, int32_t Ci, int32_t Co, int32_t L,
+                        int32_t stride, int32_t groups, void* stream);
+
 /* Vocoder optimisers: RAdam (modules/parallel_wavegan/optimizers/radam.py:57-89, the optimiser configs/tts/pwg.yaml configures) and AdamW
  * (torch.optim.AdamW; HiFi-GAN's adam_b1 / adam_b2) over a LIST of float32 tensors as they lie in memory, and the global L2 norm of a list of
  * gradients with clip_grad_norm_'s coefficient - csrc/voc_optim.hpp.  p, g, m, v, n are HOST arrays of `count` device pointers / element
