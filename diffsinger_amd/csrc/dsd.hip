@@ -1441,6 +1441,7 @@ extern "C" int dsd_debug_layer_timeline(dsd_handle* h, int32_t layer, int32_t t,
 #include "voc_abi.hpp"
 #include "fs2_loss.hpp"
 #include "fs2_regulate.hpp"
+#include "fs2_dropout.hpp"
 #include "voc_stft_abi.hpp"
 #include "voc_stft_loss_abi.hpp"
 #include "voc_mel_abi.hpp"

@@ -31,7 +31,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
+from . import _lib, dropout as _dropout
 from .hparams import hparams
 
 ACT = {'none': 0, 'relu': 1, 'gelu': 2, 'mish': 3}
@@ -502,7 +502,11 @@ class _FromCM(torch.autograd.Function):
 
 
 def _drop(x: torch.Tensor, p: float, training: bool) -> torch.Tensor:
-    return F.dropout(x, p, True) if (training and p > 0) else x
+    """F.dropout in train mode - or, with dropout.enable(), the counter-based HIP op (dropout.py); the identity in eval mode and at p == 0."""
+    if not (training and p > 0):
+        return x
+    st = _dropout.current()
+    return _dropout.dropout_op(x, p, st) if st is not None else F.dropout(x, p, True)
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -626,18 +630,26 @@ class EncSALayer(nn.Module):
 
     def forward_cm(self, x, T, keep, pad_u8, col_keep=None):
         """EncSALayer.forward (common_layers.py:565-588) on a cm tensor; col_keep: see frame_keep (zero where the frame axis has ended for every row); with self.training and dropout > 0 the three dropouts of the reference
-        (:576, TransformerFFNLayer :520, :584) sit between the convolutions and their residual adds, so those run unfused."""
+        (:576, TransformerFFNLayer :520, :584) sit between the convolutions and their residual adds, so those run unfused - as torch ops, or, with
+        dropout.enable(), as dropout_op / dropout_add_keep_op (dropout + residual + padding mask in one launch, no saved mask; sites in this
+        order: attention residual, FFN hidden, FFN residual)."""
         a, f = self.self_attn, self.ffn
         p = self.dropout if self.training else 0.0
+        st = _dropout.current() if p > 0 else None
         y = layer_norm_cm(x, T, self.layer_norm1.weight, self.layer_norm1.bias, 1e-5)
         qkv = conv1d_cm(y, T, a.in_proj_weight, a._pin)
         o = attention_cm(qkv, T, pad_u8, self.num_heads)
-        if p > 0:
+        if st is not None:
+            x = _dropout.dropout_add_keep_op(conv1d_cm(o, T, a.out_proj.weight, a._pout), x, keep, T, p, st)
+        elif p > 0:
             x = (x + F.dropout(conv1d_cm(o, T, a.out_proj.weight, a._pout), p, True)) * _keep_cm(keep, x.shape[2])
         else:
             x = conv1d_cm(o, T, a.out_proj.weight, a._pout, residual=x, keep=keep)
         y = layer_norm_cm(x, T, self.layer_norm2.weight, self.layer_norm2.bias, 1e-5, keep=col_keep)
         hdn = conv1d_cm(y, T, f.ffn_1.weight, f._p1, f.ffn_1.bias, scale=f.kernel_size ** -0.5, act=f.act)
+        if st is not None:
+            out = conv1d_cm(_dropout.dropout_op(hdn, p, st), T, f.ffn_2.weight, f._p2, f.ffn_2.bias)
+            return _dropout.dropout_add_keep_op(out, x, keep, T, p, st)
         if p > 0:
             out = conv1d_cm(F.dropout(hdn, p, True), T, f.ffn_2.weight, f._p2, f.ffn_2.bias)
             return (x + F.dropout(out, p, True)) * _keep_cm(keep, x.shape[2])
@@ -786,7 +798,7 @@ def _run_pred_convs(convs, packs, xc, T, keep):
         conv, ln = seq[1], seq[3]
         y = conv1d_cm(xc, T, conv.weight, pk, conv.bias)            # ReLU is fused into the LayerNorm kernel's load
         xc = layer_norm_cm(y, T, ln.weight, ln.bias, 1e-12, relu_in=True, keep=keep)
-        xc = seq[4](xc)                                             # nn.Dropout(predictor_dropout): identity in eval mode (tts_modules.py:94, :216)
+        xc = _drop(xc, seq[4].p, seq[4].training)                   # nn.Dropout(predictor_dropout): identity in eval mode (tts_modules.py:94, :216)
     return xc
 
 

@@ -16,7 +16,7 @@ mask (`mel.abs().sum(-1) == 0`), the positional-embedding lookup and denorm_f0 a
 Training (PitchExtractionTask, tasks/tts/pe.py): in train mode the forward runs under autograd.  BatchNorm1d takes the batch statistics and
 updates its running buffers in one launch (dsf_batch_norm_train, Prenet's ReLU and padding mask inside), its backward is one launch;
 GroupNorm + ReLU + residual has dsf_group_norm_bwd; the convolutions, LayerNorms and layout changes are the FastSpeech2 training operators
-(fs2.py); the predictor's dropout is torch's F.dropout.  pe_losses is the task's loss dict on the fused dsf_f0_loss, pe_training_step the task's
+(fs2.py); the predictor's dropout is torch's F.dropout (or, with dropout.enable(), the counter-based HIP op of dropout.py).  pe_losses is the task's loss dict on the fused dsf_f0_loss, pe_training_step the task's
 _training_step.  Not covered: synchronising BatchNorm statistics or buffers across ranks (the reference's DDP does not sync the statistics
 either), Prenet strides other than 1, ConvBlock norms other than 'gn', a fused dropout."""
 from __future__ import annotations

@@ -363,6 +363,30 @@ int dsf_dur_loss_bwd(const float* dur_pred, const int64_t* mel2ph, const int64_t
 int dsf_length_regulate(const int64_t* dur, const float* logdur, float offset, const uint8_t* dur_padding, float alpha, int64_t* dur_out,
                         int64_t* mel2ph, int32_t* mel_len, int32_t B, int32_t T_txt, int32_t T_out, void* stream);
 
+/* Training dropout of FastSpeech2 with a counter-based mask (csrc/fs2_dropout.hpp): nothing of the activation's size is saved for the backward,
+ * which regenerates the mask, and a host can restate it exactly.
+ * The mask of a fp32 buffer, by the flat index i (int64) of an element:  q = i >> 2, j = i & 3,
+ *     w = Philox4x32-10(counter = (q lo32, q hi32, site, step lo32), key = (seed lo32, seed hi32))[j];   element i is KEPT iff w >= thr
+ * (unsigned 32-bit compare).  The HOST forms thr = min(round(p * 2^32), 2^32 - 1) and scale = (float)(1.0 / (1.0 - p)) (in double, then
+ * narrowed) for p in the open interval (0, 1).  state is a DEVICE cell of two 64-bit words, {seed, step}, read by the kernels: a captured
+ * training step stays valid when the step advances.  site numbers the dropout call inside the step.
+ * dsf_dropout_grid_elements     the elements one pass of a launch's grid covers (larger buffers are covered by a grid-stride loop).
+ * dsf_dropout                   y[i] = kept ? x[i] * scale : 0 for i < n; x, y any fp32 buffers (float4 accesses when both are 16-byte
+ *                               aligned, one element per access otherwise - the mask is that of the buffer's own flat indices either way).
+ *                               Its own adjoint: the backward is the same call on dy.
+ * dsf_dropout_add_keep          x, res, y channel-major [B][C][TS], TS = padded_frames(T); keep [B][T] float 0 / 1 or NULL (all ones):
+ *                                   y = keep[b][t] * (res + (kept ? x * scale : 0)) for t < T, 0 for t in [T, TS)
+ *                               each product and sum rounded once (no contraction).
+ * dsf_dropout_add_keep_bwd      dres = dy * keep, dx = kept ? dres * scale : 0, both 0 in [T, TS); dres may be NULL.
+ * Refused (DSD_ERR_INVALID) before any HIP call: a null pointer (except keep, dres), n < 1, B / C / T < 1, thr == 0, B above 65535 or
+ * C * TS above 2^31 - 1. */
+int64_t dsf_dropout_grid_elements(void);
+int dsf_dropout(const float* x, float* y, int64_t n, const uint64_t* state, uint32_t site, uint32_t thr, float scale, void* stream);
+int dsf_dropout_add_keep(const float* x, const float* res, const float* keep, float* y, int32_t B, int32_t C, int32_t T, const uint64_t* state,
+                         uint32_t site, uint32_t thr, float scale, void* stream);
+int dsf_dropout_add_keep_bwd(const float* dy, const float* keep, float* dx, float* dres, int32_t B, int32_t C, int32_t T, const uint64_t* state,
+                             uint32_t site, uint32_t thr, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
