@@ -32,7 +32,8 @@ SYMBOLS_FS2 = ['dsf_padded_frames', 'dsf_packed_floats', 'dsf_pack_weight', 'dsf
                'dsf_f0_loss_workspace_floats', 'dsf_f0_loss', 'dsf_f0_loss_bwd',
                'dsf_stack_workspace_floats', 'dsf_set_stack_mode', 'dsf_set_stack_conv', 'dsf_get_stack_conv', 'dsf_set_wgrad_dual', 'dsf_debug_trb_timeline', 'dsf_stack_offsets', 'dsf_stack_forward', 'dsf_stack_backward', 'dsf_wgrad2_workspace_floats', 'dsf_conv1d_wgrad2', 'dsf_wgrad_probe', 'dsf_wgrad_probe_read',
                'dsf_fs2_loss_workspace_floats', 'dsf_mel_loss', 'dsf_mel_loss_bwd', 'dsf_dur_loss', 'dsf_dur_loss_bwd', 'dsf_length_regulate',
-               'dsf_dropout_grid_elements', 'dsf_dropout', 'dsf_dropout_add_keep', 'dsf_dropout_add_keep_bwd']
+               'dsf_dropout_grid_elements', 'dsf_dropout', 'dsf_dropout_add_keep', 'dsf_dropout_add_keep_bwd',
+               'dsf_cwt2f0', 'dsf_cwt2f0_bwd', 'dsf_cwt_pitch_loss_workspace_floats', 'dsf_cwt_pitch_loss', 'dsf_cwt_pitch_loss_bwd']
 
 # every symbol include/dsv.h declares (the HiFi-GAN / NSF-HiFi-GAN generator ops)
 SYMBOLS_VOC = ['dsv_padded_samples', 'dsv_packed_floats', 'dsv_pack_weight', 'dsv_pad_rows', 'dsv_conv1d', 'dsv_conv1d_multi', 'dsv_set_lean', 'dsv_noise_conv', 'dsv_sine_source',
@@ -219,6 +220,12 @@ def load():
     lib.dsf_dropout.argtypes = [vp, vp, i64, vp, u32, u32, f32, vp]
     lib.dsf_dropout_add_keep.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, u32, u32, f32, vp]
     lib.dsf_dropout_add_keep_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, u32, u32, f32, vp]
+    lib.dsf_cwt2f0.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, f32, f32, vp]
+    lib.dsf_cwt2f0_bwd.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i32, i32, i32, f32, i32, f32, f32, vp]
+    lib.dsf_cwt_pitch_loss_workspace_floats.argtypes = []
+    lib.dsf_cwt_pitch_loss_workspace_floats.restype = i64
+    lib.dsf_cwt_pitch_loss.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp]
+    lib.dsf_cwt_pitch_loss_bwd.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp]
     lib.dsv_padded_samples.argtypes = [i32]
     lib.dsv_padded_samples.restype = i32
     lib.dsv_packed_floats.argtypes = [i32, i32, i32]

@@ -1440,6 +1440,7 @@ extern "C" int dsd_debug_layer_timeline(dsd_handle* h, int32_t layer, int32_t t,
 #include "train_abi.hpp"
 #include "voc_abi.hpp"
 #include "fs2_loss.hpp"
+#include "fs2_cwt.hpp"
 #include "fs2_regulate.hpp"
 #include "fs2_dropout.hpp"
 #include "voc_stft_abi.hpp"

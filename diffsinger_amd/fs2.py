@@ -399,6 +399,93 @@ def pitch_coarse_op(f0: torch.Tensor, uv, mel2ph, hp):
     return den, coarse
 
 
+# Where FastSpeech2.cwt2f0_norm and the cwt objective run: `infer` = dsf_cwt2f0 in the inference forward (beside _GLUE; see DESIGN.md section 7 for
+# why it is off by default: the fused glue is pledged to the BITS of the torch op sequence, and a fused mean / deviation cannot carry them),
+# `loss` = dsf_cwt_pitch_loss inside losses.fs2_losses.  A forward that needs cwt2f0_norm's gradient takes the operator whenever _GLUE is on.
+_CWT_NATIVE = {'infer': False, 'loss': True}
+
+
+def set_cwt_native(infer: Optional[bool] = None, loss: Optional[bool] = None):
+    """A/B switch of the tests and of the measurement; None leaves a route as it is."""
+    if infer is not None:
+        _CWT_NATIVE['infer'] = bool(infer)
+    if loss is not None:
+        _CWT_NATIVE['loss'] = bool(loss)
+
+
+class _Cwt2F0(torch.autograd.Function):
+    """dsf_cwt2f0 / dsf_cwt2f0_bwd."""
+
+    @staticmethod
+    def forward(ctx, cwt, mean, std, live, T_out, std_scale, norm, f0_mean, f0_std):
+        B, T, _ = cwt.shape
+        dev = cwt.device
+        out = torch.empty(B, T_out, device=dev, dtype=torch.float32)
+        stats = torch.empty(B, 2, device=dev, dtype=torch.float64)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dsf_cwt2f0(cwt.data_ptr(), cwt.stride(0), cwt.stride(1), cwt.stride(2), mean.data_ptr(), std.data_ptr(),
+                                              live.data_ptr() if live is not None else None, out.data_ptr(), stats.data_ptr(), B, T, T_out,
+                                              std_scale, norm, f0_mean, f0_std, _stream(dev)), 'dsf_cwt2f0')
+        ctx.save_for_backward(cwt, mean, std, stats, *(() if live is None else (live,)))
+        ctx.cfg = (T_out, std_scale, norm, f0_mean, f0_std)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        cwt, mean, std, stats, *rest = ctx.saved_tensors
+        live = rest[0] if rest else None
+        T_out, std_scale, norm, f0_mean, f0_std = ctx.cfg
+        B, T, K = cwt.shape
+        dev = cwt.device
+        g = g.contiguous()
+        # the gradient takes the strides of cwt (the slice's backward then copies it into the parent) unless cwt is an expanded view
+        dense = all(s > 0 for s in cwt.stride())
+        dcwt = torch.empty_strided((B, T, K), cwt.stride() if dense else (T * K, K, 1), device=dev, dtype=torch.float32)
+        dmean = torch.empty(B, device=dev, dtype=torch.float32)
+        dstd = torch.empty(B, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().dsf_cwt2f0_bwd(cwt.data_ptr(), cwt.stride(0), cwt.stride(1), cwt.stride(2), mean.data_ptr(), std.data_ptr(),
+                                                  live.data_ptr() if live is not None else None, stats.data_ptr(), g.data_ptr(), dcwt.data_ptr(),
+                                                  dcwt.stride(0), dcwt.stride(1), dcwt.stride(2), dmean.data_ptr(), dstd.data_ptr(), B, T, T_out,
+                                                  std_scale, norm, f0_mean, f0_std, _stream(dev)), 'dsf_cwt2f0_bwd')
+        return dcwt, dmean, dstd, None, None, None, None, None, None
+
+
+def _cwt2f0_fusable(cwt_spec, mean, std, hp) -> bool:
+    return (all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (cwt_spec, mean, std)) and cwt_spec.dim() == 3
+            and cwt_spec.shape[2] == 10 and cwt_spec.shape[1] >= 1 and mean.shape == std.shape == cwt_spec.shape[:1]
+            and hp['pitch_norm'] in ('standard', 'log'))
+
+
+def cwt2f0_op(cwt_spec: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, T_out: int, hp, *, std_scale: float = 1.0, live=None):
+    """FastSpeech2.cwt2f0_norm (fs2.py:239-245: utils/cwt.py cwt2f0, the repeat of the last frame up to T_out columns, norm_f0) as ONE launch,
+    differentiable in cwt_spec, mean and std: normalised f0 [B, T_out].  cwt_spec: [B, T, 10] CUDA fp32 with ANY strides (the first 10
+    channels of the predictor's 11 are read in place); mean, std: [B]; std_scale multiplies std (hparams['cwt_std_scale']) without a launch of
+    its own; live: a device scalar (frame_keep's count) - the row statistics then run over the first `live` frames only."""
+    for n, t in (('cwt_spec', cwt_spec), ('mean', mean), ('std', std)):
+        if not torch.is_tensor(t):
+            raise TypeError(f'cwt2f0_op: {n} must be a tensor (got {type(t).__name__})')
+        _need_hip(t, 'cwt2f0_op')
+        if t.dtype != torch.float32:
+            raise TypeError(f'cwt2f0_op: {n} must be float32 (got {t.dtype})')
+    if cwt_spec.dim() != 3 or cwt_spec.shape[2] != 10 or cwt_spec.shape[0] < 1 or cwt_spec.shape[1] < 1:
+        raise ValueError(f'cwt2f0_op: cwt_spec must be [B, T, 10] (got {tuple(cwt_spec.shape)})')
+    B, T = cwt_spec.shape[:2]
+    if tuple(mean.shape) != (B,) or tuple(std.shape) != (B,):
+        raise ValueError(f'cwt2f0_op: mean and std must be [{B}] (got {tuple(mean.shape)}, {tuple(std.shape)})')
+    if isinstance(T_out, bool) or not isinstance(T_out, (int, np.integer)) or T_out < T:
+        raise ValueError(f'cwt2f0_op: T_out must be an int >= T = {T} (got {T_out!r})')
+    if hp['pitch_norm'] not in ('standard', 'log'):
+        raise NotImplementedError(f"cwt2f0_op: pitch_norm {hp['pitch_norm']!r}")
+    if live is not None:
+        if not torch.is_tensor(live) or live.device != cwt_spec.device or live.numel() != 1:
+            raise ValueError('cwt2f0_op: live must be a one-element tensor on the device of cwt_spec')
+        live = live.detach().to(torch.float32).reshape(1)
+    norm = 1 if hp['pitch_norm'] == 'standard' else 2
+    f0_mean, f0_std = (float(hp['f0_mean']), float(hp['f0_std'])) if norm == 1 else (0.0, 1.0)
+    return _Cwt2F0.apply(cwt_spec, mean.contiguous(), std.contiguous(), live, int(T_out), float(std_scale), norm, f0_mean, f0_std)
+
+
 def _needs_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
@@ -1197,7 +1284,12 @@ class FastSpeech2(nn.Module):
         return from_cm(conv1d_cm(xc, T, self.mel_out.weight, self._pmel, self.mel_out.bias, keep=tgt_nonpadding[:, :, 0].contiguous()), T)
 
     def cwt2f0_norm(self, cwt_spec, mean, std, mel2ph, fk=None):
-        b = (torch.arange(0, 10, device=cwt_spec.device).float()[None, None, :] + 1 + 2.5) ** (-2.5)     # utils/cwt.py:118-125
+        if _GLUE and _cwt2f0_fusable(cwt_spec, mean, std, hparams) and mel2ph.shape[1] >= cwt_spec.shape[1]:
+            needs_grad = torch.is_grad_enabled() and (cwt_spec.requires_grad or mean.requires_grad or std.requires_grad)
+            if needs_grad or (_CWT_NATIVE['infer'] and _glue_ok(cwt_spec, mean, std, mel2ph)):
+                # the ~25 launches below as one (dsf_cwt2f0), differentiable (dsf_cwt2f0_bwd); float64 inside, so not the bits of the expression
+                return cwt2f0_op(cwt_spec, mean, std, mel2ph.shape[1], hparams, live=fk[1] if fk is not None else None)
+        b =(torch.arange(0, 10, device=cwt_spec.device).float()[None, None, :] + 1 + 2.5) ** (-2.5)     # utils/cwt.py:118-125
         rec = (cwt_spec * b).sum(-1)
         full = (rec - rec.mean(-1, keepdim=True)) / rec.std(-1, keepdim=True)
         if fk is None:

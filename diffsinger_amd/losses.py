@@ -6,8 +6,9 @@ the kernels of csrc/fs2_loss.hpp (include/dsf.h, "FastSpeech2 training objective
     fs2_losses(output, sample, hp, variant='fs2' | 'midi', sil_ph_ids=None)   the reference's loss dict
 
 Nothing here synchronises with the host: the word buffer is sized by the phone count, not by the data (the reference's `word_id.max()`), so a
-whole training step can be captured as a graph.  The pitch / uv / energy / cwt terms act on [B, T] vectors and are torch expressions on the
-device.  There is no CPU path: CPU tensors are refused."""
+whole training step can be captured as a graph.  The cwt terms (C / uv / f0_mean / f0_std) are one fused operator on the kernels of
+csrc/fs2_cwt.hpp ("CWT pitch"); the frame- and phone-level pitch terms and the energy term act on [B, T] vectors and are torch expressions
+on the device.  There is no CPU path: CPU tensors are refused."""
 from __future__ import annotations
 
 
@@ -159,6 +160,93 @@ def dur_loss_terms(dur_pred, mel2ph, txt_tokens, *, sil_ids=None, word_boundary=
     return _DurLoss.apply(dur_pred.contiguous(), m2p, tok, sil, wdb, lam_ph, lam_word, lam_sent)
 
 
+class _CwtPitchLoss(torch.autograd.Function):
+    """out = [C, uv, f0_mean, f0_std, sum nonpadding]; dsf_cwt_pitch_loss / dsf_cwt_pitch_loss_bwd."""
+
+    @staticmethod
+    def forward(ctx, pred, mean_pred, std_pred, spec, uv, mel2ph, mean_tgt, std_tgt, use_uv, l2, lam_f0, lam_uv):
+        lib = _lib.load()
+        B, T, Cp = pred.shape
+        ws = torch.empty(int(lib.dsf_cwt_pitch_loss_workspace_floats()), device=pred.device, dtype=torch.float32)
+        out = torch.empty(5, device=pred.device, dtype=torch.float32)
+        args = (pred.data_ptr(), pred.stride(0), pred.stride(1), pred.stride(2), spec.data_ptr(), uv.data_ptr() if use_uv else None,
+                mel2ph.data_ptr() if use_uv else None, mean_pred.data_ptr(), mean_tgt.data_ptr(), std_pred.data_ptr(), std_tgt.data_ptr(), B, T, Cp,
+                int(use_uv), int(l2), float(lam_f0), float(lam_uv))
+        with torch.cuda.device(pred.device):
+            _lib.check(lib.dsf_cwt_pitch_loss(*args, ws.data_ptr(), out.data_ptr(), _stream(pred.device)), 'dsf_cwt_pitch_loss')
+        ctx.args = args
+        ctx.save_for_backward(pred, mean_pred, std_pred, spec, uv if use_uv else spec, mel2ph if use_uv else spec, mean_tgt, std_tgt, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, *_kept, out = ctx.saved_tensors                   # kept alive: the pointers in ctx.args are theirs
+        B, T, Cp = pred.shape
+        g4 = g[:4].contiguous()
+        dp = torch.empty((B, T, Cp), device=pred.device, dtype=torch.float32)
+        dmean = torch.empty(B, device=pred.device, dtype=torch.float32)
+        dstd = torch.empty(B, device=pred.device, dtype=torch.float32)
+        with torch.cuda.device(pred.device):
+            _lib.check(_lib.load().dsf_cwt_pitch_loss_bwd(*ctx.args, out.data_ptr(), g4.data_ptr(), dp.data_ptr(), dmean.data_ptr(), dstd.data_ptr(),
+                                                          _stream(pred.device)), 'dsf_cwt_pitch_loss_bwd')
+        return (dp, dmean, dstd) + (None,) * 9
+
+
+def _f32_on(name, t, shape, dev):
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
+        raise ValueError(f'{name}: a CUDA tensor on {dev} is required (there is no CPU path)')
+    if t.dtype != torch.float32:
+        raise ValueError(f'{name}: float32 required, got {t.dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{name}: shape {tuple(shape)} expected, got {tuple(t.shape)}')
+    return t
+
+
+def cwt_pitch_loss_terms(cwt_out, cwt_spec, uv, mel2ph, f0_mean_pred, f0_mean, f0_std_pred, f0_std, *, cwt_loss='l1', use_uv=True, lambda_f0=1.0,
+                         lambda_uv=1.0):
+    """[C, uv, f0_mean, f0_std] of the cwt branch of FastSpeech2Task.add_pitch_loss (tasks/tts/fs2.py:233-247), each times its lambda, from one
+    pass over cwt_out: a [4] tensor (uv reads 0 without use_uv).  cwt_out: the cwt predictor's output [B, T, 10 (+ 1 with use_uv: the uv
+    logit is the LAST channel)] fp32 with any strides; cwt_spec [B, T, 10]; uv [B, T] float; mel2ph [B, T] (nonpadding = mel2ph != 0); the four
+    statistics [B].  Gradients: cwt_out (the whole tensor in one launch), f0_mean_pred, f0_std_pred."""
+    if cwt_loss not in ('l1', 'l2'):
+        raise NotImplementedError(f"cwt_pitch_loss_terms: cwt_loss {cwt_loss!r} (ssim goes through mel_loss_terms)")
+    if not torch.is_tensor(cwt_out) or not cwt_out.is_cuda:
+        raise ValueError('cwt_out: a CUDA tensor is required (there is no CPU path)')
+    need = 11 if use_uv else 10
+    if cwt_out.dtype != torch.float32 or cwt_out.dim() != 3 or cwt_out.shape[0] < 1 or cwt_out.shape[1] < 1 or cwt_out.shape[2] < need:
+        raise ValueError(f'cwt_out: float32 [B, T, {need}+] required, got {cwt_out.dtype} {tuple(cwt_out.shape)}')
+    B, T = cwt_out.shape[:2]
+    dev = cwt_out.device
+    spec = _f32_on('cwt_spec', cwt_spec, (B, T, 10), dev).contiguous()
+    stats = [_f32_on(n, t, (B,), dev) for n, t in (('f0_mean_pred', f0_mean_pred), ('f0_std_pred', f0_std_pred), ('f0_mean', f0_mean), ('f0_std', f0_std))]
+    if any(t.requires_grad for t in (spec, stats[2], stats[3])):
+        raise NotImplementedError('cwt_pitch_loss_terms: the targets get no gradient')
+    uv_c = m2p = None
+    if use_uv:
+        uv_c = _f32_on('uv', uv, (B, T), dev).contiguous()
+        m2p = _i64('mel2ph', mel2ph, (B, T))
+    out = _CwtPitchLoss.apply(cwt_out, stats[0].contiguous(), stats[1].contiguous(), spec, uv_c, m2p, stats[2].contiguous(), stats[3].contiguous(),
+                              bool(use_uv), cwt_loss == 'l2', float(lambda_f0), float(lambda_uv))
+    return out[:4]
+
+
+def _cwt_loss_fusable(output, sample, hp) -> bool:
+    """Plain CUDA fp32 tensors of the shapes the operator takes; anything else keeps the torch expressions (and their error messages)."""
+    c = output['cwt']
+    if not (torch.is_tensor(c) and c.is_cuda and c.dtype == torch.float32 and c.dim() == 3 and c.shape[2] == (11 if hp['use_uv'] else 10)
+            and c.shape[0] >= 1 and c.shape[1] >= 1):
+        return False
+    B, T = c.shape[:2]
+    want = [(sample['cwt_spec'], (B, T, 10)), (output['f0_mean'], (B,)), (output['f0_std'], (B,)), (sample['f0_mean'], (B,)), (sample['f0_std'], (B,))]
+    if hp['use_uv']:
+        want.append((sample['uv'], (B, T)))
+        m = sample['mel2ph']
+        if not (torch.is_tensor(m) and m.device == c.device and m.dtype == torch.int64 and tuple(m.shape) == (B, T)):
+            return False
+    return all(torch.is_tensor(t) and t.device == c.device and t.dtype == torch.float32 and tuple(t.shape) == s for t, s in want) and not any(
+        t.requires_grad for t in (sample['cwt_spec'], sample['f0_mean'], sample['f0_std']))
+
+
 def parse_mel_loss(spec: str) -> dict:
     """hparams['mel_loss'] -> {name: lambda} as FastSpeech2Task.__init__ builds it (tasks/tts/fs2.py:34-44)."""
     out = {}
@@ -243,21 +331,39 @@ def _add_pitch_loss(output, sample, hp, losses):
     nonpadding = (mel2ph != 0).float()
     if hp['pitch_type'] == 'cwt':
         cwt_pred = output['cwt'][:, :, :10]
-        if hp.get('cwt_loss', 'l1') == 'l1':
-            c = F.l1_loss(cwt_pred, sample['cwt_spec'])
-        elif hp['cwt_loss'] == 'l2':
-            c = F.mse_loss(cwt_pred, sample['cwt_spec'])
-        elif hp['cwt_loss'] == 'ssim':
-            c = mel_loss_terms(cwt_pred, sample['cwt_spec'], bias=20.0, l1=False, ssim=True)[1]
+        if hp.get('cwt_add_f0_loss') and hp['use_uv']:
+            raise ValueError("cwt_add_f0_loss with use_uv: the reference itself fails there - add_f0_loss indexes channel 1 of the one-channel "
+                             "f0_cwt_[:, :, None] (tasks/tts/fs2.py:257); set use_uv false to train with the f0 term")
+        from . import fs2 as _fs2
+        if hp.get('cwt_loss', 'l1') in ('l1', 'l2') and _fs2._CWT_NATIVE['loss'] and _cwt_loss_fusable(output, sample, hp):
+            # C / uv / f0_mean / f0_std from one pass over the predictor's output (dsf_cwt_pitch_loss), the gradient of the parent in one more
+            t = cwt_pitch_loss_terms(output['cwt'], sample['cwt_spec'], uv if hp['use_uv'] else None, mel2ph, output['f0_mean'], sample['f0_mean'],
+                                     output['f0_std'], sample['f0_std'], cwt_loss=hp.get('cwt_loss', 'l1'), use_uv=bool(hp['use_uv']),
+                                     lambda_f0=hp['lambda_f0'], lambda_uv=hp['lambda_uv'] if hp['use_uv'] else 0.0)
+            losses['C'] = t[0]
+            if hp['use_uv']:
+                losses['uv'] = t[1]
+            losses['f0_mean'], losses['f0_std'] = t[2], t[3]
         else:
-            raise NotImplementedError(f"cwt_loss {hp['cwt_loss']!r}")
-        losses['C'] = c * hp['lambda_f0']
-        if hp['use_uv']:
-            losses['uv'] = _masked_mean(F.binary_cross_entropy_with_logits(output['cwt'][:, :, -1], uv, reduction='none'), nonpadding) * hp['lambda_uv']
-        losses['f0_mean'] = F.l1_loss(output['f0_mean'], sample['f0_mean']) * hp['lambda_f0']
-        losses['f0_std'] = F.l1_loss(output['f0_std'], sample['f0_std']) * hp['lambda_f0']
+            if hp.get('cwt_loss', 'l1') == 'l1':
+                c = F.l1_loss(cwt_pred, sample['cwt_spec'])
+            elif hp['cwt_loss'] == 'l2':
+                c = F.mse_loss(cwt_pred, sample['cwt_spec'])
+            elif hp['cwt_loss'] == 'ssim':
+                c = mel_loss_terms(cwt_pred, sample['cwt_spec'], bias=20.0, l1=False, ssim=True)[1]
+            else:
+                raise NotImplementedError(f"cwt_loss {hp['cwt_loss']!r}")
+            losses['C'] = c * hp['lambda_f0']
+            if hp['use_uv']:
+                losses['uv'] = _masked_mean(F.binary_cross_entropy_with_logits(output['cwt'][:, :, -1], uv, reduction='none'), nonpadding) * hp['lambda_uv']
+            losses['f0_mean'] = F.l1_loss(output['f0_mean'], sample['f0_mean']) * hp['lambda_f0']
+            losses['f0_std'] = F.l1_loss(output['f0_std'], sample['f0_std']) * hp['lambda_f0']
         if hp.get('cwt_add_f0_loss'):
-            raise NotImplementedError('cwt_add_f0_loss: the f0 term goes through the model (cwt2f0_norm, tasks/tts/fs2.py:245-247); add it beside fs2_losses')
+            # tasks/tts/fs2.py:245-247: the f0 the model would synthesise from its own cwt / mean / std (no cwt_std_scale, no frame_keep:
+            # the reference calls cwt2f0_norm with its defaults), through add_f0_loss without uv (:254-267)
+            from .pe import f0_loss_terms
+            f0_cwt = _fs2.cwt2f0_op(cwt_pred, output['f0_mean'], output['f0_std'], mel2ph.shape[1], hp)
+            losses['f0'] = f0_loss_terms(f0_cwt[:, :, None], f0, None, nonpadding, use_uv=False, pitch_loss=hp['pitch_loss'], lam_f0=hp['lambda_f0'])[1]
     elif hp['pitch_type'] == 'frame':
         p_pred = output['pitch_pred']
         if hp['use_uv']:

@@ -387,6 +387,46 @@ int dsf_dropout_add_keep(const float* x, const float* res, const float* keep, fl
 int dsf_dropout_add_keep_bwd(const float* dy, const float* keep, float* dx, float* dres, int32_t B, int32_t C, int32_t T, const uint64_t* state,
                              uint32_t site, uint32_t thr, float scale, void* stream);
 
+/* CWT pitch (pitch_type: cwt; csrc/fs2_cwt.hpp): FastSpeech2.cwt2f0_norm, its gradient, and the cwt branch of add_pitch_loss.  No allocation,
+ * no synchronisation, no host read of a device value, every sum in a fixed order (two evaluations are bitwise equal); float64 arithmetic on
+ * fp32 operands.
+ * dsf_cwt2f0            modules/fastspeech/fs2.py:239-245 as ONE launch.  cwt [B][T][10] fp32 with element strides sb / st / sc (the live call
+ *                       passes the first 10 channels of the 11-wide predictor output); mean, std [B] (DEVICE); live: NULL or a DEVICE float
+ *                       scalar, the number of leading frames that enter the row statistics (frame_keep's count; values >= T mean T).
+ *                           rec[t] = sum_k cwt[t][k] (k + 3.5)^-2.5;  mu, sigma = mean and unbiased (N - 1) deviation of rec over the first N
+ *                           frames;  z = (rec - mu) / sigma for EVERY t < T;  f0 = exp(z std std_scale + mean);  columns T .. T_out - 1
+ *                           repeat column T - 1;  out [B][T_out] = log2(f0) (pitch_norm 2) or (f0 - f0_mean) / f0_std (pitch_norm 1).
+ *                       stats [B][2] float64 receives mu and 1 / sigma.  The order of the two reductions depends on N alone - not on T, not
+ *                       on T_out: on the frames they share, a forward over a longer allocation with the same live carries the same bits.
+ *                       N < 2 or a constant row is a division by zero (non-finite values, as in the reference), not an error.
+ * dsf_cwt2f0_bwd        ONE launch: from d_out [B][T_out] (contiguous): d_cwt [B][T][10] with element strides gsb / gst / gsc (only the 10
+ *                       scale channels are written), d_mean [B], d_std [B] (with std_scale).  stats = the forward's.
+ * dsf_cwt_pitch_loss    tasks/tts/fs2.py:233-247 in two launches.  pred [B][T][channels] fp32 with element strides sb / st / sc: channels
+ *                       0 .. 9 are the scales, the LAST channel is the uv logit under use_uv (channels >= 10 + use_uv); cwt_spec [B][T][10],
+ *                       uv [B][T] fp32, mel2ph [B][T] int64 contiguous (uv, mel2ph may be NULL without use_uv); the four statistics [B].
+ *                           out[0] = mean(|pred - cwt_spec|) lam_f0 over B T 10 (l2: the square)
+ *                           out[1] = sum(BCEWithLogits(logit, uv) np) / sum(np) lam_uv, np = (mel2ph != 0), BCE as max(x, 0) - x z +
+ *                                    log1p(exp(-|x|)); 0 without use_uv; NaN (0 / 0) for an empty mask, as the reference's expression
+ *                           out[2] = mean(|f0_mean_pred - f0_mean|) lam_f0,  out[3] = mean(|f0_std_pred - f0_std|) lam_f0,  out[4] = sum(np)
+ *                       workspace: dsf_cwt_pitch_loss_workspace_floats() floats, 8-byte aligned.
+ * dsf_cwt_pitch_loss_bwd  ONE launch: d_pred [B][T][channels] contiguous - the whole parent tensor: scale channels, the uv logit, zeros
+ *                       between them - d_f0_mean_pred, d_f0_std_pred [B] of grad_out . out[0..3] (grad_out a DEVICE [4]); stats = the forward's out.
+ * Refused (DSD_ERR_INVALID) before any HIP call: a null pointer (except live; uv / mel2ph without use_uv), B / T < 1, T_out < T, B above
+ * 65535 (cwt2f0), pitch_norm outside {1, 2}, f0_std == 0 under pitch_norm 1, too few channels. */
+int dsf_cwt2f0(const float* cwt, int64_t sb, int64_t st, int64_t sc, const float* mean, const float* std, const float* live, float* out,
+               double* stats, int32_t B, int32_t T, int32_t T_out, float std_scale, int32_t pitch_norm, float f0_mean, float f0_std, void* stream);
+int dsf_cwt2f0_bwd(const float* cwt, int64_t sb, int64_t st, int64_t sc, const float* mean, const float* std, const float* live,
+                   const double* stats, const float* d_out, float* d_cwt, int64_t gsb, int64_t gst, int64_t gsc, float* d_mean, float* d_std,
+                   int32_t B, int32_t T, int32_t T_out, float std_scale, int32_t pitch_norm, float f0_mean, float f0_std, void* stream);
+int64_t dsf_cwt_pitch_loss_workspace_floats(void);
+int dsf_cwt_pitch_loss(const float* pred, int64_t sb, int64_t st, int64_t sc, const float* cwt_spec, const float* uv, const int64_t* mel2ph,
+                       const float* f0_mean_pred, const float* f0_mean, const float* f0_std_pred, const float* f0_std, int32_t B, int32_t T,
+                       int32_t channels, int32_t use_uv, int32_t l2, float lam_f0, float lam_uv, float* workspace, float* out, void* stream);
+int dsf_cwt_pitch_loss_bwd(const float* pred, int64_t sb, int64_t st, int64_t sc, const float* cwt_spec, const float* uv, const int64_t* mel2ph,
+                           const float* f0_mean_pred, const float* f0_mean, const float* f0_std_pred, const float* f0_std, int32_t B, int32_t T,
+                           int32_t channels, int32_t use_uv, int32_t l2, float lam_f0, float lam_uv, const float* stats, const float* grad_out,
+                           float* d_pred, float* d_f0_mean_pred, float* d_f0_std_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
