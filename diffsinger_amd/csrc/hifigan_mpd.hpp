@@ -42,7 +42,7 @@ constexpr int kHgpTileN = 64;                                // positions per wo
 constexpr int kHgpKb = 32;                                   // channels per K block
 constexpr int kHgpMaxPhase = 3;                              // the stride
 constexpr int kHgpWgM = 128, kHgpWgN = 32, kHgpWgLd = 33;    // k_hgp_wgrad: co x ci per workgroup, LDS row stride
-constexpr int kHgpEdgeSplit = 4096;                          // positions per workgroup of k_hgp_edge_wgrad
+constexpr int kHgpEdgeSplit = 4096;                          // positions per workgroup of k_hgp_edge_wgrad and k_hgs_first_wgrad (hifigan_msd.hpp)
 constexpr int kHgpLossThreads = 256, kHgpLossMaxBlocks = 256;
 
 // ---- fold -------------------------------------------------------------------------------------------------------------------------------------

@@ -15,10 +15,6 @@ extern "C" int64_t dsv_hgp_folded_samples(int32_t T, int32_t period) {
     return Tp - T >= T ? -1 : Tp;
 }
 
-static int hgp_check_slope(const char* who, float slope) {
-    if (!(slope > 0.f && slope < 1.f)) return fail(DSD_ERR_INVALID, "%s: negative_slope=%g must be in (0, 1)", who, (double)slope);
-    return DSD_OK;
-}
 static int hgp_check_stride(const char* who, int S) {
     if (S != 1 && S != 3) return fail(DSD_ERR_INVALID, "%s: stride=%d must be 1 or 3", who, S);
     return DSD_OK;
@@ -34,7 +30,7 @@ extern "C" int dsv_hgp_fold(const float* x, float* out, int32_t B, int32_t T, in
     const int64_t Tp = dsv_hgp_folded_samples(T, period);
     if (Tp < 0) return fail(DSD_ERR_INVALID, "dsv_hgp_fold: T=%d, period=%d: the reflect pad must be shorter than the signal (period in [1, 64])", T, period);
     DSD_TRY(voc_check_period_shape("dsv_hgp_fold", B, (int)(Tp / period), period));
-    if (ld_x < T || ld_x > ((int64_t)1 << 31)) return fail(DSD_ERR_INVALID, "dsv_hgp_fold: row stride %lld must be in [T=%d, 2^31]", (long long)ld_x, T);
+    DSD_TRY(voc_check_row_stride("dsv_hgp_fold", ld_x, T));
     DSD_TRY(voc_check_disjoint("dsv_hgp_fold", x, (B - 1) * ld_x + T, out, (int64_t)B * Tp));
     hipLaunchKernelGGL(k_hgp_fold, dim3((unsigned)((Tp + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, out, T, (long long)ld_x, (int)Tp);
     HIP_TRY(hipGetLastError());
@@ -77,8 +73,8 @@ extern "C" int dsv_hgp_first(const float* x, const float* w, const float* bias, 
     if (!x || !w || !out) return fail(DSD_ERR_INVALID, "dsv_hgp_first: null argument");
     DSD_TRY(voc_check_period_shape("dsv_hgp_first", B, H, period));
     DSD_TRY(hgp_check_stride("dsv_hgp_first", stride));
-    DSD_TRY(hgp_check_slope("dsv_hgp_first", slope));
-    if (C < 1 || C > 65535) return fail(DSD_ERR_INVALID, "dsv_hgp_first: C=%d must be in [1, 65535]", C);
+    DSD_TRY(voc_check_slope("dsv_hgp_first", slope));
+    DSD_TRY(voc_check_grid_channels("dsv_hgp_first", C));
     const int Ho = hgp_out_h(H, stride);
     DSD_TRY(voc_check_disjoint("dsv_hgp_first", x, (int64_t)B * H * period, out, (int64_t)B * C * Ho * period));
     hipLaunchKernelGGL(k_hgp_first, dim3((unsigned)((Ho * period + 255) / 256), (unsigned)C, (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, w, bias, out,
@@ -92,7 +88,7 @@ extern "C" int dsv_hgp_first_backward(const float* g0, const float* x, const flo
     if (!g0 || !x || !w || !workspace || !dw) return fail(DSD_ERR_INVALID, "dsv_hgp_first_backward: null argument");
     DSD_TRY(voc_check_period_shape("dsv_hgp_first_backward", B, H, period));
     DSD_TRY(hgp_check_stride("dsv_hgp_first_backward", stride));
-    if (C < 1 || C > 65535) return fail(DSD_ERR_INVALID, "dsv_hgp_first_backward: C=%d must be in [1, 65535]", C);
+    DSD_TRY(voc_check_grid_channels("dsv_hgp_first_backward", C));
     const int Ho = hgp_out_h(H, stride);
     const size_t gplane = (size_t)Ho * period;
     DSD_TRY(hgp_edge_grad("dsv_hgp_first_backward", g0, nullptr, x, workspace, dw, db, C, kHgpK, kHgpPad, stride, B, Ho, H, period, (size_t)C * gplane, gplane,
@@ -109,7 +105,7 @@ extern "C" int dsv_hgp_first_backward(const float* g0, const float* x, const flo
 extern "C" int dsv_hgp_post(const float* a, const float* w, const float* bias, float* out, int32_t B, int32_t C, int32_t H, int32_t period, void* stream) {
     if (!a || !w || !out) return fail(DSD_ERR_INVALID, "dsv_hgp_post: null argument");
     DSD_TRY(voc_check_period_shape("dsv_hgp_post", B, H, period));
-    if (C < 1 || C > 65535) return fail(DSD_ERR_INVALID, "dsv_hgp_post: C=%d must be in [1, 65535]", C);
+    DSD_TRY(voc_check_grid_channels("dsv_hgp_post", C));
     DSD_TRY(voc_check_disjoint("dsv_hgp_post", a, (int64_t)B * C * H * period, out, (int64_t)B * H * period));
     hipLaunchKernelGGL(k_hgp_post, dim3((unsigned)((H * period + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, w, bias, out, C, H, period);
     HIP_TRY(hipGetLastError());
@@ -120,8 +116,8 @@ extern "C" int dsv_hgp_post_backward(const float* gp, const float* gp2, const fl
                                      float* db, float* ga, int32_t B, int32_t C, int32_t H, int32_t period, float slope, void* stream) {
     if (!gp || !a || !w || !workspace || !dw || !ga) return fail(DSD_ERR_INVALID, "dsv_hgp_post_backward: null argument");
     DSD_TRY(voc_check_period_shape("dsv_hgp_post_backward", B, H, period));
-    DSD_TRY(hgp_check_slope("dsv_hgp_post_backward", slope));
-    if (C < 1 || C > 65535) return fail(DSD_ERR_INVALID, "dsv_hgp_post_backward: C=%d must be in [1, 65535]", C);
+    DSD_TRY(voc_check_slope("dsv_hgp_post_backward", slope));
+    DSD_TRY(voc_check_grid_channels("dsv_hgp_post_backward", C));
     const size_t plane = (size_t)H * period;
     DSD_TRY(voc_check_disjoint("dsv_hgp_post_backward", a, (int64_t)B * C * plane, ga, (int64_t)B * C * plane));
     DSD_TRY(hgp_edge_grad("dsv_hgp_post_backward", gp, gp2, a, workspace, dw, db, C, kHgpPostK, 1, 1, B, H, H, period, plane, 0, (size_t)C * plane, plane, 0,
@@ -166,7 +162,7 @@ extern "C" int dsv_hgp_conv(const float* x, const float* w_packed, const float* 
     DSD_TRY(voc_check_period_shape("dsv_hgp_conv", B, H, period));
     DSD_TRY(hgp_check_channels("dsv_hgp_conv", Ci, Co));
     DSD_TRY(hgp_check_stride("dsv_hgp_conv", stride));
-    DSD_TRY(hgp_check_slope("dsv_hgp_conv", slope));
+    DSD_TRY(voc_check_slope("dsv_hgp_conv", slope));
     const int Ho = hgp_out_h(H, stride);
     DSD_TRY(voc_check_disjoint("dsv_hgp_conv", x, (int64_t)B * Ci * H * period, out, (int64_t)B * Co * Ho * period));
     HgpGemmParams p{};
@@ -183,7 +179,7 @@ extern "C" int dsv_hgp_conv_dgrad(const float* g, const float* w_packed, const f
     DSD_TRY(voc_check_period_shape("dsv_hgp_conv_dgrad", B, H, period));
     DSD_TRY(hgp_check_channels("dsv_hgp_conv_dgrad", Ci, Co));
     DSD_TRY(hgp_check_stride("dsv_hgp_conv_dgrad", stride));
-    DSD_TRY(hgp_check_slope("dsv_hgp_conv_dgrad", slope));
+    DSD_TRY(voc_check_slope("dsv_hgp_conv_dgrad", slope));
     const int Ho = hgp_out_h(H, stride);
     DSD_TRY(voc_check_disjoint("dsv_hgp_conv_dgrad", g, (int64_t)B * Co * Ho * period, out, (int64_t)B * Ci * H * period));
     HgpGemmParams p{};

@@ -8,7 +8,8 @@
 // no tail.  Nothing is read or written outside [B][C][L]: a window sample outside [0, L) is a zero in LDS, never a load.
 //
 //   k_hgs_first / _first_dx / _first_wgrad      the 1 -> C, K = 15 layer on the vector ALU; parameter gradients as float64 partial sums per split of
-//                             the position axis (reduced by k_hgp_edge_reduce).
+//                             the position axis (kHgpEdgeSplit positions, the period discriminator's workspace layout, reduced by its
+//                             k_hgp_edge_reduce).
 //   k_hgs_pack                a layer's weights [Co][Ci / g][41] -> the A stream of k_hgs_gemm (forward, or the data gradient's per-phase matrices).
 //   k_hgs_gemm<MT, E>         forward OR data gradient of a grouped layer on the fp32 MFMA (MT = 32: v_mfma_f32_32x32x2_f32, MT = 16:
 //                             v_mfma_f32_16x16x4_f32).  A workgroup owns one group, one batch row and NQ columns (64 or 128 positions): RB row blocks x
@@ -34,7 +35,6 @@ namespace dsd {
 
 constexpr int kHgsK = 41, kHgsPad = 20;                      // the grouped layers
 constexpr int kHgsFirstK = 15, kHgsFirstPad = 7;
-constexpr int kHgsFirstSplit = 4096;                         // positions per workgroup of k_hgs_first_wgrad
 constexpr int kHgsMaxPhase = 4;
 constexpr int kHgsWgCi = 8;                                  // input channels per workgroup of k_hgs_wgrad
 constexpr int kHgsWgCols = kHgsWgCi * kHgsK;                 // 328
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void k_hgs_first_dx(const float* __restrict__ 
 __global__ __launch_bounds__(256) void k_hgs_first_wgrad(const float* __restrict__ g0, const float* __restrict__ x, float* __restrict__ part, int C, int T,
                                                          long long ld, long long npos) {
     const int tid = threadIdx.x, c = blockIdx.x, split = blockIdx.y;
-    const long long n0 = (long long)split * kHgsFirstSplit, n1 = min(npos, n0 + kHgsFirstSplit);
+    const long long n0 = (long long)split * kHgpEdgeSplit, n1 = min(npos, n0 + kHgpEdgeSplit);
     double s[kHgsFirstK + 1];
 #pragma unroll
     for (int k = 0; k <= kHgsFirstK; ++k) s[k] = 0.0;

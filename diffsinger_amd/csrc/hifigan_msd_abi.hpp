@@ -33,10 +33,6 @@ static int hgs_check_geom(const char* who, int Ci, int Co, int S, int G, const H
 }
 static int hgs_out_len(int L, int S) { return (L - 1) / S + 1; }    // K = 41, padding 20
 static int hgs_log2(int s) { return s == 4 ? 2 : s == 2 ? 1 : 0; }
-static int hgs_check_slope(const char* who, float slope) {
-    if (!(slope > 0.f && slope < 1.f)) return fail(DSD_ERR_INVALID, "%s: negative_slope=%g must be in (0, 1)", who, (double)slope);
-    return DSD_OK;
-}
 // an operand that is only read (`in`, may be null: skipped) against a range the call writes; inputs may overlap one another
 static int hgs_disjoint(const char* who, const float* in, int64_t n_in, const float* out, int64_t n_out) {
     if (!in || !out) return DSD_OK;
@@ -50,16 +46,16 @@ extern "C" int32_t dsv_hgs_out_len(int32_t L, int32_t stride) { return (L < 1 ||
 // ---- first layer ------------------------------------------------------------------------------------------------------------------------------------
 extern "C" int64_t dsv_hgs_first_workspace_floats(int32_t B, int32_t T, int32_t C) {
     if (!voc_shape_ok(B, T) || C < 1 || C > 65535) return -1;
-    return (((int64_t)B * T + kHgsFirstSplit - 1) / kHgsFirstSplit) * C * (kHgsFirstK + 1);
+    return (((int64_t)B * T + kHgpEdgeSplit - 1) / kHgpEdgeSplit) * C * (kHgsFirstK + 1);
 }
 
 extern "C" int dsv_hgs_first(const float* x, const float* w, const float* bias, float* out, int32_t B, int32_t C, int32_t T, int64_t ld_x, float slope,
                              void* stream) {
     if (!x || !w || !out) return fail(DSD_ERR_INVALID, "dsv_hgs_first: null argument");
     DSD_TRY(hgs_check_shape("dsv_hgs_first", B, T));
-    DSD_TRY(hgs_check_slope("dsv_hgs_first", slope));
-    if (C < 1 || C > 65535) return fail(DSD_ERR_INVALID, "dsv_hgs_first: C=%d must be in [1, 65535]", C);
-    if (ld_x < T || ld_x > ((int64_t)1 << 31)) return fail(DSD_ERR_INVALID, "dsv_hgs_first: row stride %lld must be in [T=%d, 2^31]", (long long)ld_x, T);
+    DSD_TRY(voc_check_slope("dsv_hgs_first", slope));
+    DSD_TRY(voc_check_grid_channels("dsv_hgs_first", C));
+    DSD_TRY(voc_check_row_stride("dsv_hgs_first", ld_x, T));
     DSD_TRY(voc_check_disjoint("dsv_hgs_first", x, (B - 1) * ld_x + T, out, (int64_t)B * C * T));
     DSD_TRY(hgs_disjoint("dsv_hgs_first", w, (int64_t)C * kHgsFirstK, out, (int64_t)B * C * T));
     DSD_TRY(hgs_disjoint("dsv_hgs_first", bias, C, out, (int64_t)B * C * T));
@@ -73,11 +69,10 @@ extern "C" int dsv_hgs_first_backward(const float* g0, const float* x, const flo
                                       int32_t C, int32_t T, int64_t ld_x, void* stream) {
     if (!g0 || !x || !w || !workspace || !dw) return fail(DSD_ERR_INVALID, "dsv_hgs_first_backward: null argument");
     DSD_TRY(hgs_check_shape("dsv_hgs_first_backward", B, T));
-    if (C < 1 || C > 65535) return fail(DSD_ERR_INVALID, "dsv_hgs_first_backward: C=%d must be in [1, 65535]", C);
-    if (ld_x < T || ld_x > ((int64_t)1 << 31))
-        return fail(DSD_ERR_INVALID, "dsv_hgs_first_backward: row stride %lld must be in [T=%d, 2^31]", (long long)ld_x, T);
+    DSD_TRY(voc_check_grid_channels("dsv_hgs_first_backward", C));
+    DSD_TRY(voc_check_row_stride("dsv_hgs_first_backward", ld_x, T));
     const int64_t npos = (int64_t)B * T;
-    const int64_t nsplit = (npos + kHgsFirstSplit - 1) / kHgsFirstSplit;
+    const int64_t nsplit = (npos + kHgpEdgeSplit - 1) / kHgpEdgeSplit;
     if (nsplit > 65535) return fail(DSD_ERR_INVALID, "dsv_hgs_first_backward: %lld splits exceed 65535 workgroups", (long long)nsplit);
     {   // every range the call reads against every range it writes, and the written ranges against one another
         const int64_t n_ws = nsplit * C * (kHgsFirstK + 1), n_g = (int64_t)B * C * T, n_x = (B - 1) * ld_x + T, n_w = (int64_t)C * kHgsFirstK;
@@ -172,7 +167,7 @@ extern "C" int dsv_hgs_gconv(const float* x, const float* w_packed, const float*
     const HgsGeom* ge;
     DSD_TRY(hgs_check_geom("dsv_hgs_gconv", Ci, Co, stride, groups, &ge));
     DSD_TRY(hgs_check_shape("dsv_hgs_gconv", B, L));
-    DSD_TRY(hgs_check_slope("dsv_hgs_gconv", slope));
+    DSD_TRY(voc_check_slope("dsv_hgs_gconv", slope));
     if ((uintptr_t)w_packed & 15) return fail(DSD_ERR_INVALID, "dsv_hgs_gconv: the packed weights must be aligned to 16 bytes");
     const int Lo = hgs_out_len(L, stride), co_g = Co / groups, ci_g = Ci / groups;
     DSD_TRY(voc_check_disjoint("dsv_hgs_gconv", x, (int64_t)B * Ci * L, out, (int64_t)B * Co * Lo));
@@ -192,7 +187,7 @@ extern "C" int dsv_hgs_gconv_dgrad(const float* g, const float* w_packed, const 
     const HgsGeom* ge;
     DSD_TRY(hgs_check_geom("dsv_hgs_gconv_dgrad", Ci, Co, stride, groups, &ge));
     DSD_TRY(hgs_check_shape("dsv_hgs_gconv_dgrad", B, L));
-    DSD_TRY(hgs_check_slope("dsv_hgs_gconv_dgrad", slope));
+    DSD_TRY(voc_check_slope("dsv_hgs_gconv_dgrad", slope));
     if ((uintptr_t)w_packed & 15) return fail(DSD_ERR_INVALID, "dsv_hgs_gconv_dgrad: the packed weights must be aligned to 16 bytes");
     const int Lo = hgs_out_len(L, stride), co_g = Co / groups, ci_g = Ci / groups;
     DSD_TRY(voc_check_disjoint("dsv_hgs_gconv_dgrad", g, (int64_t)B * Co * Lo, out, (int64_t)B * Ci * L));

@@ -17,6 +17,24 @@ static int voc_check_f64_workspace(const char* who, const void* ptr, const char*
     return DSD_OK;
 }
 
+// the leaky ReLU's slope
+static int voc_check_slope(const char* who, float slope) {
+    if (!(slope > 0.f && slope < 1.f)) return fail(DSD_ERR_INVALID, "%s: negative_slope=%g must be in (0, 1)", who, (double)slope);
+    return DSD_OK;
+}
+
+// C channels of an edge layer (1 -> C or C -> 1): C is a grid dimension
+static int voc_check_grid_channels(const char* who, int C) {
+    if (C < 1 || C > 65535) return fail(DSD_ERR_INVALID, "%s: C=%d must be in [1, 65535]", who, C);
+    return DSD_OK;
+}
+
+// rows of T samples `ld` floats apart
+static int voc_check_row_stride(const char* who, int64_t ld, int T) {
+    if (ld < T || ld > ((int64_t)1 << 31)) return fail(DSD_ERR_INVALID, "%s: row stride %lld must be in [T=%d, 2^31]", who, (long long)ld, T);
+    return DSD_OK;
+}
+
 // splits of `len` samples that cover L
 static int voc_splits(int L, int len) { return (L + len - 1) / len; }
 

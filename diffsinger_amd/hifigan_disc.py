@@ -37,10 +37,18 @@ discriminators always, the spectral-normed one in eval(); in train() its buffers
 disc_s_op forward is 15 launches: first layer 1, per grouped layer 2 (dsv_hgs_pack, dsv_hgs_gconv), the dense layer 3 (dsv_pack_weight's two, dsv_hgp_conv
 at period 1), conv_post 1 (dsv_hgp_post).  Its backward is 30 + s + x: conv_post 3, the dense layer 5 (weight gradient, bias gradient, the pack's
 two, data gradient), per grouped layer 4 (weight gradient, bias gradient, dsv_hgs_pack of the phase matrices, data gradient; + 1 reduction where
-dsv_hgs_wgrad_splits > 1: s counts those layers), the first layer 2 and x = 1 when the input requires a gradient; a layer without a bias is one less."""
+dsv_hgs_wgrad_splits > 1: s counts those layers), the first layer 2 and x = 1 when the input requires a gradient; a layer without a bias is one less.
+
+DiscPFunction and DiscSFunction are the two autograd nodes; their forwards differ (the fold, the per-layer kernels) and so do the first and the
+grouped layers of their backwards.  Everything else exists once and serves both: _hand_out / _pair_results (the outputs, or their halves under
+pair=True, and the inverse), _gather_cots (the cotangents' addresses; _join alone owns the adjacent-halves rule), _grad_buffers, _post_backward,
+_dense_backward (the scale discriminator's layer 6 is the period discriminator's layer 4 at period 1, stride 1; the first layers keep a
+kernel set each), _check_params (driven by a list of weight shapes), _check_pair and the modules' base classes _Disc (all four) and
+_SingleDisc (the two single discriminators' _params).  _grad_buffers allocates every gradient before the first launch, not layer by layer."""
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+import math
+from typing import Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -146,6 +154,90 @@ def _join(cr, cg, shape, dev):
     return t.data_ptr(), t
 
 
+# ---- what the two autograd nodes share ----------------------------------------------------------------------------------------------------------
+def _hand_out(out, maps, pair):
+    """what a node's forward returns: (out,) + maps, or with pair=True every buffer as its two halves, (out_r, out_g, the maps' first halves, the
+    second halves)"""
+    if not pair:
+        return (out,) + tuple(maps)
+    Bh = out.shape[0] // 2
+    return (out[:Bh], out[Bh:]) + tuple(m[:Bh] for m in maps) + tuple(m[Bh:] for m in maps)
+
+
+def _pair_results(res, n):
+    """_hand_out's inverse for pair=True and n maps: ((out_r, fmap_r), (out_g, fmap_g)), every tensor a half of the node's buffers"""
+    return (res[0], list(res[2:2 + n])), (res[1], list(res[2 + n:]))
+
+
+def _gather_cots(cots, pair, shapes, dev):
+    """the cotangents a node's backward receives, for _hand_out's outputs over maps of `shapes` (the last one conv_post's, whose flattening is out)
+    -> (gp1, gp2, cot, keep): the addresses of the one or two cotangents of conv_post's output (gp2 None where one arrives; a zero buffer where
+    none does), the per-map addresses (None where absent) and the tensors that keep all of them alive"""
+    n = len(shapes)
+    out_shape = (shapes[-1][0], math.prod(shapes[-1][1:]))
+    keep, cot = [], []
+    if pair:
+        g_out, k = _join(cots[0], cots[1], out_shape, dev)
+        keep.append(k)
+        for l in range(n):
+            a, k = _join(cots[2 + l], cots[2 + n + l], shapes[l], dev)
+            cot.append(a); keep.append(k)
+    else:
+        t = _f32c(cots[0])
+        g_out = None if t is None else t.data_ptr()
+        keep.append(t)
+        for l in range(n):
+            t = _f32c(cots[1 + l])
+            cot.append(None if t is None else t.data_ptr()); keep.append(t)
+    gp1, gp2 = (g_out, cot[-1]) if g_out is not None else (cot[-1], None)
+    if gp1 is None:                                             # nothing arrives on the output: its cotangent is zero
+        z = torch.zeros(out_shape, device=dev, dtype=torch.float32)
+        keep.append(z)
+        gp1 = z.data_ptr()
+    return gp1, gp2, cot, keep
+
+
+def _grad_buffers(wshapes, has_b, dev):
+    """(dws, dbs): one weight gradient per shape, one bias gradient (None where the layer has no bias)"""
+    return ([torch.empty(s, device=dev, dtype=torch.float32) for s in wshapes],
+            [torch.empty(s[0], device=dev, dtype=torch.float32) if hb else None for s, hb in zip(wshapes, has_b)])
+
+
+def _hp(a):
+    """(H, p) of an activation [B][C][H][p], or [B][C][L] of the scale discriminator: (L, 1)"""
+    return a.shape[2], (a.shape[3] if a.dim() == 4 else 1)
+
+
+def _post_backward(gp1, gp2, a, w, cot, ws_e, dw, db, slope):
+    """conv_post's backward over its input a: parameter gradients into dw / db through the workspace ws_e -> the gradient with respect to the
+    pre-activation behind a, which includes the cotangent `cot` of a"""
+    H, p = _hp(a)
+    G = torch.empty(a.shape, device=a.device, dtype=torch.float32)
+    _call('dsv_hgp_post_backward', 3, a.device, gp1, gp2, a.data_ptr(), w.data_ptr(), cot, ws_e.data_ptr(), dw.data_ptr(), _lib.ptr(db), G.data_ptr(),
+          a.shape[0], a.shape[1], H, p, slope)
+    return G
+
+
+def _dense_backward(lib, G, a, w, cot, dw, db, S, slope):
+    """backward of a dense K = 5 layer w [Co][Ci][5] of stride S over its input a, G the gradient with respect to its pre-activation:
+    dsv_hgp_conv_wgrad into dw / db, dsv_pack_weight per input phase, dsv_hgp_conv_dgrad -> the gradient with respect to the pre-activation
+    behind a, which includes the cotangent `cot` of a.  The scale discriminator's layer 6 is the period discriminator's layer 4 at period 1."""
+    dev, B = a.device, a.shape[0]
+    (H, p), (co, ci) = _hp(a), w.shape[:2]
+    nws = lib.dsv_hgp_wgrad_workspace_floats(B, ci, co, G.shape[2], p)
+    ws_w = torch.empty(nws, device=dev, dtype=torch.float32) if nws else None
+    _call('dsv_hgp_conv_wgrad', 1 + (1 if nws else 0) + (0 if db is None else 1), dev, G.data_ptr(), a.data_ptr(), _lib.ptr(ws_w), dw.data_ptr(),
+          _lib.ptr(db), B, ci, co, H, p, S)
+    packed = torch.empty(lib.dsv_hgp_dgrad_packed_offset(ci, co, S, S), device=dev, dtype=torch.float32)
+    for r in range(S):
+        ks = _phase_taps(lib, S, r)
+        m = (w if len(ks) == _K else w[:, :, ks]).permute(1, 0, 2).contiguous()     # [ci][co][taps of the phase]; stride 1: the one phase holds all five
+        _call('dsv_pack_weight', 2, dev, m.data_ptr(), ci, co, len(ks), packed.data_ptr() + 4 * lib.dsv_hgp_dgrad_packed_offset(ci, co, S, r))
+    Gn = torch.empty(a.shape, device=dev, dtype=torch.float32)
+    _call('dsv_hgp_conv_dgrad', 1, dev, G.data_ptr(), packed.data_ptr(), cot, a.data_ptr(), Gn.data_ptr(), B, ci, co, H, p, S, slope)
+    return Gn
+
+
 class DiscPFunction(torch.autograd.Function):
     """x [B][1][T], six weights [Co][Ci][K][1], six biases (None where absent) -> (out [B][H p], a_0 .. a_4, a_5 = conv_post's output [B][1][H][p]):
     views of the node's buffers.  pair=True: B = 2 Bh and every output is handed out as its two halves, (out_r, out_g, the six maps' first halves,
@@ -175,12 +267,7 @@ class DiscPFunction(torch.autograd.Function):
         _call('dsv_hgp_post', 1, dev, acts[4].data_ptr(), wd[5].data_ptr(), _lib.ptr(b[5]), post.data_ptr(), B, _CH[5], hs[5], p)
         ctx.save_for_backward(xf, *wd, *acts)
         ctx.meta = (B, T, p, float(slope), bool(pair), hs, [t is not None for t in bs])
-        out = post.view(B, hs[5] * p)
-        maps = acts + [post]
-        if not pair:
-            return (out,) + tuple(maps)
-        Bh = B // 2
-        return (out[:Bh], out[Bh:]) + tuple(m[:Bh] for m in maps) + tuple(m[Bh:] for m in maps)
+        return _hand_out(post.view(B, hs[5] * p), acts + [post], pair)
 
     @staticmethod
     @once_differentiable
@@ -190,57 +277,13 @@ class DiscPFunction(torch.autograd.Function):
         wd, acts = rest[:_NCONV + 1], rest[_NCONV + 1:]
         B, T, p, slope, pair, hs, has_b = ctx.meta
         dev = xf.device
-        keep = []                                               # tensors whose addresses are in flight
-        if pair:
-            g_out, k = _join(cots[0], cots[1], (B, hs[5] * p), dev)
-            keep.append(k)
-            cot = []
-            for l in range(_NCONV + 1):
-                a, k = _join(cots[2 + l], cots[2 + _NCONV + 1 + l], (B, _CH[l + 1] if l < _NCONV else 1, hs[l + 1] if l < _NCONV else hs[5], p), dev)
-                cot.append(a); keep.append(k)
-        else:
-            t = _f32c(cots[0])
-            g_out = None if t is None else t.data_ptr()
-            keep.append(t)
-            cot = []
-            for l in range(_NCONV + 1):
-                t = _f32c(cots[1 + l])
-                cot.append(None if t is None else t.data_ptr()); keep.append(t)
-        gp1, gp2 = (g_out, cot[5]) if g_out is not None else (cot[5], None)
-        if gp1 is None:                                         # nothing arrives on the output: its cotangent is zero
-            z = torch.zeros(B, hs[5] * p, device=dev, dtype=torch.float32)
-            keep.append(z)
-            gp1 = z.data_ptr()
-        dws: List[Optional[torch.Tensor]] = [None] * (_NCONV + 1)
-        dbs: List[Optional[torch.Tensor]] = [None] * (_NCONV + 1)
-
-        def grads(l, co, ci, k):
-            dws[l] = torch.empty(co, ci, k, 1, device=dev, dtype=torch.float32)
-            dbs[l] = torch.empty(co, device=dev, dtype=torch.float32) if has_b[l] else None
-
-        grads(5, 1, _CH[5], _KPOST)
+        gp1, gp2, cot, keep = _gather_cots(cots, pair, [a.shape for a in acts] + [(B, 1, hs[5], p)], dev)    # keep: tensors whose addresses are in flight
+        dws, dbs = _grad_buffers([tuple(w.shape) + (1,) for w in wd], has_b, dev)
         ws_e = torch.empty(max(lib.dsv_hgp_edge_workspace_floats(B, hs[5], p, _CH[5], _KPOST), lib.dsv_hgp_edge_workspace_floats(B, hs[1], p, _CH[1], _K)),
                            device=dev, dtype=torch.float32)
-        G = torch.empty(B, _CH[5], hs[5], p, device=dev, dtype=torch.float32)
-        _call('dsv_hgp_post_backward', 3, dev, gp1, gp2, acts[4].data_ptr(), wd[5].data_ptr(), cot[4], ws_e.data_ptr(), dws[5].data_ptr(), _lib.ptr(dbs[5]),
-              G.data_ptr(), B, _CH[5], hs[5], p, slope)
+        G = _post_backward(gp1, gp2, acts[4], wd[5], cot[4], ws_e, dws[5], dbs[5], slope)
         for l in range(_NCONV - 1, 0, -1):
-            ci, co, S = _CH[l], _CH[l + 1], _STRIDES[l]
-            grads(l, co, ci, _K)
-            nws = lib.dsv_hgp_wgrad_workspace_floats(B, ci, co, hs[l + 1], p)
-            ws_w = torch.empty(nws, device=dev, dtype=torch.float32) if nws else None
-            _call('dsv_hgp_conv_wgrad', 1 + (1 if nws else 0) + (1 if has_b[l] else 0), dev, G.data_ptr(), acts[l - 1].data_ptr(), _lib.ptr(ws_w),
-                  dws[l].data_ptr(), _lib.ptr(dbs[l]), B, ci, co, hs[l], p, S)
-            packed = torch.empty(lib.dsv_hgp_dgrad_packed_offset(ci, co, S, S), device=dev, dtype=torch.float32)
-            for r in range(S):
-                ks = _phase_taps(lib, S, r)
-                m = wd[l][:, :, ks].permute(1, 0, 2).contiguous()                      # [ci][co][taps of the phase]
-                _call('dsv_pack_weight', 2, dev, m.data_ptr(), ci, co, len(ks), packed.data_ptr() + 4 * lib.dsv_hgp_dgrad_packed_offset(ci, co, S, r))
-            Gn = torch.empty(B, ci, hs[l], p, device=dev, dtype=torch.float32)
-            _call('dsv_hgp_conv_dgrad', 1, dev, G.data_ptr(), packed.data_ptr(), cot[l - 1], acts[l - 1].data_ptr(), Gn.data_ptr(), B, ci, co, hs[l], p, S,
-                  slope)
-            G = Gn
-        grads(0, _CH[1], 1, _K)
+            G = _dense_backward(lib, G, acts[l - 1], wd[l], cot[l - 1], dws[l], dbs[l], _STRIDES[l], slope)
         need_dx = ctx.needs_input_grad[0]
         dxf = torch.empty(B, hs[0] * p, device=dev, dtype=torch.float32) if need_dx else None
         _call('dsv_hgp_first_backward', 3 if need_dx else 2, dev, G.data_ptr(), xf.data_ptr(), wd[0].data_ptr(), ws_e.data_ptr(), dws[0].data_ptr(),
@@ -268,18 +311,27 @@ def _check_px(x, period, who):
     return hs
 
 
-def _check_params(x, weights, biases, slope, who):
-    if len(weights) != _NCONV + 1 or len(biases) != _NCONV + 1:
-        raise ValueError(f'{who}: six weights and six biases (None where absent), got {len(weights)} and {len(biases)}')
+_P_SHAPES = [(_CH[l + 1], _CH[l], _K, 1) for l in range(_NCONV)] + [(1, _CH[_NCONV], _KPOST, 1)]
+
+
+def _check_params(x, weights, biases, slope, who, shapes=_P_SHAPES, n='six'):
+    """plain weights of `shapes` ([Co] first) and biases [Co] or None, float32 on x's device; n: their number in words, for the message"""
+    if len(weights) != len(shapes) or len(biases) != len(shapes):
+        raise ValueError(f'{who}: {n} weights and {n} biases (None where absent), got {len(weights)} and {len(biases)}')
     if not 0.0 < float(slope) < 1.0:
         raise ValueError(f'{who}: slope={slope} must be in (0, 1)')
-    for i, w in enumerate(weights):
-        want = (_CH[i + 1], _CH[i], _K, 1) if i < _NCONV else (1, _CH[_NCONV], _KPOST, 1)
-        if not isinstance(w, torch.Tensor) or tuple(w.shape) != want or w.dtype != torch.float32 or w.device != x.device:
-            raise ValueError(f'{who}: weights[{i}] must be float32 {want} on {x.device}')
-        bi = biases[i]
-        if bi is not None and (tuple(bi.shape) != (want[0],) or bi.dtype != torch.float32 or bi.device != x.device):
-            raise ValueError(f'{who}: biases[{i}] must be float32 ({want[0]},) on {x.device}, got {bi.dtype} {tuple(bi.shape)} on {bi.device}')
+
+    def bad(t, want):
+        return not isinstance(t, torch.Tensor) or tuple(t.shape) != want or t.dtype != torch.float32 or t.device != x.device
+
+    def what(t):
+        return f'{t.dtype} {tuple(t.shape)} on {t.device}' if isinstance(t, torch.Tensor) else type(t).__name__
+
+    for i, (w, bi, want) in enumerate(zip(weights, biases, shapes)):
+        if bad(w, want):
+            raise ValueError(f'{who}: weights[{i}] must be float32 {want} on {x.device}, got {what(w)}')
+        if bi is not None and bad(bi, want[:1]):
+            raise ValueError(f'{who}: biases[{i}] must be float32 ({want[0]},) on {x.device}, got {what(bi)}')
 
 
 def disc_p_op(x, period: int, weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]], slope: float = LRELU_SLOPE):
@@ -295,9 +347,7 @@ def disc_p_op(x, period: int, weights: Sequence[torch.Tensor], biases: Sequence[
 
 def _disc_p_pair(yy, period, weights, biases, slope):
     """disc_p_op over cat(y, y_hat): ((out_r, fmap_r), (out_g, fmap_g)), every tensor a half of the node's buffers"""
-    res = DiscPFunction.apply(yy, period, float(slope), True, *weights, *biases)
-    n = _NCONV + 1
-    return (res[0], list(res[2:2 + n])), (res[1], list(res[2 + n:]))
+    return _pair_results(DiscPFunction.apply(yy, period, float(slope), True, *weights, *biases), _NCONV + 1)
 
 
 class FeatureLossFunction(torch.autograd.Function):
@@ -350,7 +400,39 @@ def feature_loss(fmap_r, fmap_g):
     return FeatureLossFunction.apply(len(rs), *[t.contiguous() for t in rs], *[t.contiguous() for t in gs])
 
 
-class DiscriminatorP(nn.Module):
+class _Disc(nn.Module):
+    """what the four discriminator modules share: members that are _WN holders (directly or in `discriminators`), no mel input"""
+
+    def remove_weight_norm(self):
+        for m in self.modules():
+            if isinstance(m, _WN):
+                m.remove_weight_norm()
+
+    def _refuse_mel(self, mel):
+        if mel is not None:
+            raise NotImplementedError(f'{type(self).__name__} on HIP: use_cond (a mel input) is not supported')
+
+
+class _SingleDisc(_Disc):
+    """one discriminator: convs and conv_post hold its parameters"""
+
+    @staticmethod
+    def _weight(m):
+        return torch._weight_norm(m.weight_v, m.weight_g, 0) if hasattr(m, 'weight_g') else m.weight
+
+    def _params(self):
+        mods = list(self.convs) + [self.conv_post]
+        return [self._weight(m) for m in mods], [m.bias for m in mods]
+
+
+def _check_pair(y, y_hat, who):
+    """y_hat against a checked y: the second half of the batch of 2 B"""
+    _check_pwg_x(y_hat, who)
+    if y_hat.shape != y.shape or y_hat.device != y.device:
+        raise ValueError(f'{who}: y {tuple(y.shape)} on {y.device} against y_hat {tuple(y_hat.shape)} on {y_hat.device}')
+
+
+class DiscriminatorP(_SingleDisc):
     """modules/hifigan/hifigan.py:181-227.  forward(x [B,1,T], mel=None) -> (out [B, H p], fmap: six maps [B, C, H_l, p]), differentiable with respect
     to x and every parameter.  convs[l] / conv_post hold weight_g [Co,1,1,1], weight_v [Co,Ci,K,1], bias (or weight after remove_weight_norm())."""
 
@@ -373,23 +455,13 @@ class DiscriminatorP(nn.Module):
         self.convs = nn.ModuleList([_WN((_CH[l + 1], _CH[l], _K, 1), True, True) for l in range(_NCONV)])
         self.conv_post = _WN((1, _CH[_NCONV], _KPOST, 1), True, True)
 
-    def remove_weight_norm(self):
-        for m in self.modules():
-            if isinstance(m, _WN):
-                m.remove_weight_norm()
-
-    def _params(self):
-        mods = list(self.convs) + [self.conv_post]
-        return [torch._weight_norm(m.weight_v, m.weight_g, 0) if hasattr(m, 'weight_g') else m.weight for m in mods], [m.bias for m in mods]
-
     def forward(self, x, mel=None):
-        if mel is not None:
-            raise NotImplementedError('DiscriminatorP on HIP: use_cond (a mel input) is not supported')
+        self._refuse_mel(mel)
         ws, bs = self._params()
         return disc_p_op(x, self.period, ws, bs, LRELU_SLOPE)
 
 
-class MultiPeriodDiscriminator(nn.Module):
+class MultiPeriodDiscriminator(_Disc):
     """modules/hifigan/hifigan.py:230-250: periods 2, 3, 5, 7, 11.  forward(y, y_hat, mel=None) -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs).  d(y) and
     d(y_hat) run as one batch of 2 B per period (weight norm has no per-call state: the two calls of the reference use identical weights)."""
 
@@ -397,18 +469,11 @@ class MultiPeriodDiscriminator(nn.Module):
         super().__init__()
         self.discriminators = nn.ModuleList([DiscriminatorP(p, use_cond=use_cond, c_in=c_in) for p in _PERIODS])
 
-    def remove_weight_norm(self):
-        for d in self.discriminators:
-            d.remove_weight_norm()
-
     def forward(self, y, y_hat, mel=None):
-        if mel is not None:
-            raise NotImplementedError('MultiPeriodDiscriminator on HIP: use_cond (a mel input) is not supported')
+        self._refuse_mel(mel)
         for d in self.discriminators:
             _check_px(y, d.period, 'MultiPeriodDiscriminator')
-        _check_pwg_x(y_hat, 'MultiPeriodDiscriminator')
-        if y_hat.shape != y.shape or y_hat.device != y.device:
-            raise ValueError(f'MultiPeriodDiscriminator: y {tuple(y.shape)} on {y.device} against y_hat {tuple(y_hat.shape)} on {y_hat.device}')
+        _check_pair(y, y_hat, 'MultiPeriodDiscriminator')
         yy = torch.cat([y, y_hat]).contiguous()
         rs, gs, frs, fgs = [], [], [], []
         for d in self.discriminators:
@@ -469,12 +534,7 @@ class DiscSFunction(torch.autograd.Function):
         _call('dsv_hgp_post', 1, dev, acts[6].data_ptr(), wd[7].data_ptr(), _lib.ptr(b[7]), post.data_ptr(), B, _S_LAYERS[7][0], ls[7], 1)
         ctx.save_for_backward(x, *wd, *acts)
         ctx.meta = (B, T, ld, float(slope), bool(pair), ls, [t is not None for t in bs])
-        out = post.view(B, ls[7])
-        maps = acts + [post]
-        if not pair:
-            return (out,) + tuple(maps)
-        Bh = B // 2
-        return (out[:Bh], out[Bh:]) + tuple(m[:Bh] for m in maps) + tuple(m[Bh:] for m in maps)
+        return _hand_out(post.view(B, ls[7]), acts + [post], pair)
 
     @staticmethod
     @once_differentiable
@@ -485,57 +545,14 @@ class DiscSFunction(torch.autograd.Function):
         wd, acts = rest[:n], rest[n:]
         B, T, ld, slope, pair, ls, has_b = ctx.meta
         dev = x.device
-        keep = []                                               # tensors whose addresses are in flight
-        if pair:
-            g_out, k = _join(cots[0], cots[1], (B, ls[7]), dev)
-            keep.append(k)
-            cot = []
-            for l in range(n):
-                a, k = _join(cots[2 + l], cots[2 + n + l], (B, _S_LAYERS[l][1], ls[l]), dev)
-                cot.append(a); keep.append(k)
-        else:
-            t = _f32c(cots[0])
-            g_out = None if t is None else t.data_ptr()
-            keep.append(t)
-            cot = []
-            for l in range(n):
-                t = _f32c(cots[1 + l])
-                cot.append(None if t is None else t.data_ptr()); keep.append(t)
-        gp1, gp2 = (g_out, cot[7]) if g_out is not None else (cot[7], None)
-        if gp1 is None:                                         # nothing arrives on the output: its cotangent is zero
-            z = torch.zeros(B, ls[7], device=dev, dtype=torch.float32)
-            keep.append(z)
-            gp1 = z.data_ptr()
-        dws: List[Optional[torch.Tensor]] = [None] * n
-        dbs: List[Optional[torch.Tensor]] = [None] * n
-
-        def grads(l):
-            ci, co, k, _, g = _S_LAYERS[l]
-            dws[l] = torch.empty(co, ci // g, k, device=dev, dtype=torch.float32)
-            dbs[l] = torch.empty(co, device=dev, dtype=torch.float32) if has_b[l] else None
-
-        grads(7)
+        gp1, gp2, cot, keep = _gather_cots(cots, pair, [a.shape for a in acts] + [(B, 1, ls[7])], dev)       # keep: tensors whose addresses are in flight
+        dws, dbs = _grad_buffers([w.shape for w in wd], has_b, dev)
         C = _S_LAYERS[7][0]
         ws_e = torch.empty(lib.dsv_hgp_edge_workspace_floats(B, ls[7], 1, C, _KPOST), device=dev, dtype=torch.float32)
-        G = torch.empty(B, C, ls[6], device=dev, dtype=torch.float32)
-        _call('dsv_hgp_post_backward', 3, dev, gp1, gp2, acts[6].data_ptr(), wd[7].data_ptr(), cot[6], ws_e.data_ptr(), dws[7].data_ptr(), _lib.ptr(dbs[7]),
-              G.data_ptr(), B, C, ls[7], 1, slope)
-        # the dense 1024 -> 1024 layer: the period discriminator's fifth layer at period 1
-        grads(6)
-        ci, co, k = _S_LAYERS[6][:3]
-        nws = lib.dsv_hgp_wgrad_workspace_floats(B, ci, co, ls[6], 1)
-        ws_w = torch.empty(nws, device=dev, dtype=torch.float32) if nws else None
-        _call('dsv_hgp_conv_wgrad', 1 + (1 if nws else 0) + (1 if has_b[6] else 0), dev, G.data_ptr(), acts[5].data_ptr(), _lib.ptr(ws_w), dws[6].data_ptr(),
-              _lib.ptr(dbs[6]), B, ci, co, ls[5], 1, 1)
-        packed = torch.empty(lib.dsv_hgp_dgrad_packed_offset(ci, co, 1, 1), device=dev, dtype=torch.float32)
-        m = wd[6].permute(1, 0, 2).contiguous()                 # [ci][co][k]
-        _call('dsv_pack_weight', 2, dev, m.data_ptr(), ci, co, k, packed.data_ptr())
-        Gn = torch.empty(B, ci, ls[5], device=dev, dtype=torch.float32)
-        _call('dsv_hgp_conv_dgrad', 1, dev, G.data_ptr(), packed.data_ptr(), cot[5], acts[5].data_ptr(), Gn.data_ptr(), B, ci, co, ls[5], 1, 1, slope)
-        G = Gn
+        G = _post_backward(gp1, gp2, acts[6], wd[7], cot[6], ws_e, dws[7], dbs[7], slope)
+        G = _dense_backward(lib, G, acts[5], wd[6], cot[5], dws[6], dbs[6], 1, slope)       # the period discriminator's fifth layer at period 1
         for l in range(5, 0, -1):
             ci, co, _, s, g = _S_LAYERS[l]
-            grads(l)
             nws = lib.dsv_hgs_wgrad_workspace_floats(B, ci, co, ls[l], s, g)
             ws_w = torch.empty(nws, device=dev, dtype=torch.float32) if nws else None
             _call('dsv_hgs_gconv_wgrad', 1 + (1 if nws else 0) + (1 if has_b[l] else 0), dev, G.data_ptr(), acts[l - 1].data_ptr(), _lib.ptr(ws_w),
@@ -546,7 +563,6 @@ class DiscSFunction(torch.autograd.Function):
             _call('dsv_hgs_gconv_dgrad', 1, dev, G.data_ptr(), packed.data_ptr(), cot[l - 1], acts[l - 1].data_ptr(), Gn.data_ptr(), B, ci, co, ls[l - 1], s, g,
                   slope)
             G = Gn
-        grads(0)
         C = _S_LAYERS[0][1]
         need_dx = ctx.needs_input_grad[0]
         ws_f = torch.empty(lib.dsv_hgs_first_workspace_floats(B, T, C), device=dev, dtype=torch.float32)
@@ -563,20 +579,7 @@ def _check_sx(x, who, min_t=1):
         raise ValueError(f'{who}: x has T={x.shape[2]} > 2^30 samples')
 
 
-def _check_s_params(x, weights, biases, slope, who):
-    if len(weights) != _SN_LAYERS or len(biases) != _SN_LAYERS:
-        raise ValueError(f'{who}: eight weights and eight biases (None where absent), got {len(weights)} and {len(biases)}')
-    if not 0.0 < float(slope) < 1.0:
-        raise ValueError(f'{who}: slope={slope} must be in (0, 1)')
-    for i, w in enumerate(weights):
-        ci, co, k, _, g = _S_LAYERS[i]
-        want = (co, ci // g, k)
-        if not isinstance(w, torch.Tensor) or tuple(w.shape) != want or w.dtype != torch.float32 or w.device != x.device:
-            raise ValueError(f'{who}: weights[{i}] must be float32 {want} on {x.device}')
-        bi = biases[i]
-        if bi is not None and (not isinstance(bi, torch.Tensor) or tuple(bi.shape) != (co,) or bi.dtype != torch.float32 or bi.device != x.device):
-            what = f'{bi.dtype} {tuple(bi.shape)} on {bi.device}' if isinstance(bi, torch.Tensor) else type(bi).__name__
-            raise ValueError(f'{who}: biases[{i}] must be float32 ({co},) on {x.device}, got {what}')
+_S_SHAPES = [(co, ci // g, k) for ci, co, k, _, g in _S_LAYERS]
 
 
 def _rows(x):
@@ -593,16 +596,14 @@ def disc_s_op(x, weights: Sequence[torch.Tensor], biases: Sequence[Optional[torc
     None; x float32 [B][1][T] on the device -> (out [B][L_7], fmap): the eight feature maps [B][C][L_l], views of the node's own buffers (fmap[7]
     and out are the same values).  Differentiable with respect to x, every weight and every bias; cotangents are accepted on out and on every map."""
     _check_sx(x, 'disc_s_op')
-    _check_s_params(x, weights, biases, slope, 'disc_s_op')
+    _check_params(x, weights, biases, slope, 'disc_s_op', _S_SHAPES, 'eight')
     res = DiscSFunction.apply(_rows(x), float(slope), False, *weights, *biases)
     return res[0], list(res[1:])
 
 
 def _disc_s_pair(yy, weights, biases, slope):
     """disc_s_op over cat(y, y_hat): ((out_r, fmap_r), (out_g, fmap_g)), every tensor a half of the node's buffers"""
-    res = DiscSFunction.apply(_rows(yy), float(slope), True, *weights, *biases)
-    n = _SN_LAYERS
-    return (res[0], list(res[2:2 + n])), (res[1], list(res[2 + n:]))
+    return _pair_results(DiscSFunction.apply(_rows(yy), float(slope), True, *weights, *biases), _SN_LAYERS)
 
 
 class _SN(nn.Module):
@@ -632,7 +633,7 @@ class _SN(nn.Module):
         return self.weight_orig / sigma
 
 
-class DiscriminatorS(nn.Module):
+class DiscriminatorS(_SingleDisc):
     """modules/hifigan/hifigan.py:253-286.  forward(x [B,1,T], mel=None) -> (out [B, L_7], fmap: eight maps [B, C, L_l]), differentiable with respect
     to x and every parameter.  convs[l] / conv_post hold bias and weight_g [Co,1,1], weight_v [Co,Ci/g,K] (or weight after remove_weight_norm());
     under use_spectral_norm weight_orig and the buffers weight_u, weight_v.  The normalisations are torch expressions."""
@@ -652,15 +653,9 @@ class DiscriminatorS(nn.Module):
         self.convs = nn.ModuleList(mods[:-1])
         self.conv_post = mods[-1]
 
-    def remove_weight_norm(self):
-        for m in self.modules():
-            if isinstance(m, _WN):
-                m.remove_weight_norm()
-
-    def _params(self):
-        mods = list(self.convs) + [self.conv_post]
-        ws = [m.weight() if isinstance(m, _SN) else torch._weight_norm(m.weight_v, m.weight_g, 0) if hasattr(m, 'weight_g') else m.weight for m in mods]
-        return ws, [m.bias for m in mods]
+    @staticmethod
+    def _weight(m):
+        return m.weight() if isinstance(m, _SN) else _SingleDisc._weight(m)
 
     def _check_device(self, x, who):
         p = self.conv_post.bias
@@ -668,8 +663,7 @@ class DiscriminatorS(nn.Module):
             raise ValueError(f'{who}: the parameters are {p.dtype} on {p.device}, x is on {x.device}')
 
     def forward(self, x, mel=None):
-        if mel is not None:
-            raise NotImplementedError('DiscriminatorS on HIP: use_cond (a mel input) is not supported')
+        self._refuse_mel(mel)
         _check_sx(x, 'DiscriminatorS')
         self._check_device(x, 'DiscriminatorS')
         ws, bs = self._params()
@@ -683,7 +677,7 @@ class _MeanPool(nn.Module):
         return avg_pool_op(x)
 
 
-class MultiScaleDiscriminator(nn.Module):
+class MultiScaleDiscriminator(_Disc):
     """modules/hifigan/hifigan.py:289-325: three DiscriminatorS, the first under spectral norm, behind cumulative AvgPool1d(4, 2, 1).  forward(y, y_hat,
     mel=None) -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs); T >= 4.  The weight-normed discriminators run d(y) and d(y_hat) as one batch of 2 B; the
     spectral-normed one too in eval(), but in train() as two calls, y first: its buffers move between them, as in the reference."""
@@ -694,17 +688,10 @@ class MultiScaleDiscriminator(nn.Module):
                                              DiscriminatorS(use_cond=use_cond, c_in=c_in), DiscriminatorS(use_cond=use_cond, c_in=c_in)])
         self.meanpools = nn.ModuleList([_MeanPool(), _MeanPool()])
 
-    def remove_weight_norm(self):
-        for d in self.discriminators:
-            d.remove_weight_norm()
-
     def forward(self, y, y_hat, mel=None):
-        if mel is not None:
-            raise NotImplementedError('MultiScaleDiscriminator on HIP: use_cond (a mel input) is not supported')
+        self._refuse_mel(mel)
         _check_sx(y, 'MultiScaleDiscriminator', 4)
-        _check_pwg_x(y_hat, 'MultiScaleDiscriminator')
-        if y_hat.shape != y.shape or y_hat.device != y.device:
-            raise ValueError(f'MultiScaleDiscriminator: y {tuple(y.shape)} on {y.device} against y_hat {tuple(y_hat.shape)} on {y_hat.device}')
+        _check_pair(y, y_hat, 'MultiScaleDiscriminator')
         if 2 * y.shape[0] > 65535:
             raise ValueError(f'MultiScaleDiscriminator: 2 B = {2 * y.shape[0]} exceeds 65535 rows')
         for d in self.discriminators:
@@ -720,7 +707,7 @@ class MultiScaleDiscriminator(nn.Module):
                 g, fg = d(yy[Bh:])
             else:
                 ws, bs = d._params()
-                _check_s_params(yy, ws, bs, LRELU_SLOPE, 'MultiScaleDiscriminator')
+                _check_params(yy, ws, bs, LRELU_SLOPE, 'MultiScaleDiscriminator', _S_SHAPES, 'eight')
                 (r, fr), (g, fg) = _disc_s_pair(yy, ws, bs, LRELU_SLOPE)
             rs.append(r); gs.append(g); frs.append(fr); fgs.append(fg)
         return rs, gs, frs, fgs

@@ -520,3 +520,68 @@ def fixture_inputs():
     y = 0.5 * torch.randn(FIXTURE_B, 1, FIXTURE_T, generator=gen)
     y_hat = y + 0.3 * torch.randn(FIXTURE_B, 1, FIXTURE_T, generator=gen)
     return state, y, y_hat
+
+
+# ---- what the GPU tests of the period and the scale discriminator share (tests/test_gpu_hifigan_mpd.py, tests/test_gpu_hifigan_msd.py) ---------------
+DEV = 'cuda'
+NAN = float('nan')
+GUARD = 64
+CLOSE = 1e-4                            # the module-level figure of tests/test_hifigan_mpd_host.py and tests/test_hifigan_disc_host.py
+
+
+def rnd(*shape, seed, scale=1.0):
+    return scale * torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+
+
+def within(name, got, want, bound):
+    err = (d64(got).reshape(want.shape) - want).abs()
+    ok = err <= bound
+    ratio = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
+    assert bool(ok.all()), f'{name}: {int((~ok).sum())} of {ok.numel()} outside the bound, worst error / bound {ratio:.3g}, max error {float(err.max()):.3g}'
+    return ratio
+
+
+def close(name, got, want, scale=None, tol=CLOSE):
+    scale = want if scale is None else scale
+    got = d64(got).reshape(want.shape)
+    err, big = float((got - want).abs().max()), float(scale.abs().max())
+    print(f'{name}: max error {err:.3e}, largest value {big:.3e}')
+    assert err <= tol * big, f'{name}: max error {err:.3e} against the largest value {big:.3e}'
+
+
+class Guarded:
+    """device buffers between NaN guards (16-byte aligned: the guards are 64 floats)"""
+
+    def __init__(self):
+        self.all = []
+
+    def new(self, *shape, src=None):
+        n = 1
+        for s in shape:
+            n *= s
+        raw = torch.full((n + 2 * GUARD,), NAN, device=DEV)
+        v = raw[GUARD:GUARD + n].view(*shape)
+        if src is not None:
+            v.copy_(src.reshape(shape))
+        self.all.append((raw, n))
+        return v
+
+    def check(self):
+        for raw, n in self.all:
+            assert bool(torch.isnan(raw[:GUARD]).all()) and bool(torch.isnan(raw[GUARD + n:]).all()), 'a guard was written'
+
+
+class Ops:
+    """the C ABI on the current stream; the test files add their own packing"""
+
+    def __init__(self):
+        from diffsinger_amd import _lib
+        self.L, self.lib = _lib, _lib.load()
+        self.s = torch.cuda.current_stream().cuda_stream
+
+    def call(self, name, *args):
+        self.L.check(getattr(self.lib, name)(*args, self.s), name)
+
+    @staticmethod
+    def p(t):
+        return None if t is None else t.data_ptr()

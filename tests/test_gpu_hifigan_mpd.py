@@ -13,69 +13,23 @@ Shapes (p, T), for B in {1, 3} - the smallest at which each thing can go wrong:
     (3, 300)    100, 34, 12, 4, 2: H0 = 1 mod 3, no pad
     (5, 1454)   291, 97, 33, 11, 4: H0 = 0 mod 3; the 33 seam one layer deeper
     (2, 2121)   1061, 354, 118, 40, 14: several workgroups along the positions, an odd T, the weight gradient's splits
+    (2, 4100)   2050, 684, 228, 76, 26: the first layer's parameter gradient over 3 * 684 * 2 = 4104 positions at B = 3 - a second split of the edge
+                kernel at K = 5, of 8 positions (one split at B = 1); the scale discriminator's T = 2121, B = 3 is the same seam at K = 15
     (7, 300), (11, 300)     43 .. 1 and 28 .. 1: the fixture's shape; positions no multiple of 32"""
 import pytest
 import torch
 
 from tests import hifigan_mpd_helpers as MH
+from tests.hifigan_disc_helpers import DEV, NAN, Guarded, Ops as _Ops, close, rnd, within
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
-NAN = float('nan')
-GUARD = 64
-SHAPES = [(2, 2), (11, 12), (3, 292), (3, 300), (5, 1454), (2, 2121), (7, 300), (11, 300)]
+SHAPES = [(2, 2), (11, 12), (3, 292), (3, 300), (5, 1454), (2, 2121), (2, 4100), (7, 300), (11, 300)]
 CASES = [(p, T, B) for p, T in SHAPES for B in (1, 3)]
 CLOSE, CLOSE_LOSS = 1e-4, 1e-5          # the module-level figures of tests/test_hifigan_mpd_host.py
 
 
-def rnd(*shape, seed, scale=1.0):
-    return scale * torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def within(name, got, want, bound):
-    err = (MH.d64(got).reshape(want.shape) - want).abs()
-    ok = err <= bound
-    ratio = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
-    assert bool(ok.all()), f'{name}: {int((~ok).sum())} of {ok.numel()} outside the bound, worst error / bound {ratio:.3g}, max error {float(err.max()):.3g}'
-    return ratio
-
-
-class Guarded:
-    """device buffers between NaN guards"""
-
-    def __init__(self):
-        self.all = []
-
-    def new(self, *shape, src=None):
-        n = 1
-        for s in shape:
-            n *= s
-        raw = torch.full((n + 2 * GUARD,), NAN, device=DEV)
-        v = raw[GUARD:GUARD + n].view(*shape)
-        if src is not None:
-            v.copy_(src.reshape(shape))
-        self.all.append((raw, n))
-        return v
-
-    def check(self):
-        for raw, n in self.all:
-            assert bool(torch.isnan(raw[:GUARD]).all()) and bool(torch.isnan(raw[GUARD + n:]).all()), 'a guard was written'
-
-
-class Ops:
-    def __init__(self):
-        from diffsinger_amd import _lib
-        self.L, self.lib = _lib, _lib.load()
-        self.s = torch.cuda.current_stream().cuda_stream
-
-    def call(self, name, *args):
-        self.L.check(getattr(self.lib, name)(*args, self.s), name)
-
-    @staticmethod
-    def p(t):
-        return None if t is None else t.data_ptr()
-
+class Ops(_Ops):
     def pack(self, m):
         rows, ci, kt = m.shape
         m = m.contiguous()
@@ -335,14 +289,6 @@ def _module(state):
     m = MultiPeriodDiscriminator()
     m.load_state_dict(state, strict=True)
     return m.to(DEV)
-
-
-def close(name, got, want, scale=None, tol=CLOSE):
-    scale = want if scale is None else scale
-    got = MH.d64(got).reshape(want.shape)
-    err, big = float((got - want).abs().max()), float(scale.abs().max())
-    print(f'{name}: max error {err:.3e}, largest value {big:.3e}')
-    assert err <= tol * big, f'{name}: max error {err:.3e} against the largest value {big:.3e}'
 
 
 def test_modules_against_the_fixture_and_float64(fx, inputs, restated):

@@ -21,73 +21,17 @@ import torch
 
 from tests import hifigan_disc_helpers as DH
 from tests import hifigan_msd_helpers as SH
+from tests.hifigan_disc_helpers import DEV, Guarded, Ops as _Ops, close, rnd, within
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
-NAN = float('nan')
-GUARD = 64
 TS = [1, 41, 280, 300, 513, 1024, 1030, 2121]
 CASES = [(T, B) for T in TS for B in (1, 3)]
 CLOSE, CLOSE_LOSS, CLOSE_UNIT = 1e-4, 1e-5, 1e-5        # the module-level figures of tests/test_hifigan_disc_host.py
 N = DH.N
 
 
-def rnd(*shape, seed, scale=1.0):
-    return scale * torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def within(name, got, want, bound):
-    err = (DH.d64(got).reshape(want.shape) - want).abs()
-    ok = err <= bound
-    ratio = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
-    assert bool(ok.all()), f'{name}: {int((~ok).sum())} of {ok.numel()} outside the bound, worst error / bound {ratio:.3g}, max error {float(err.max()):.3g}'
-    return ratio
-
-
-def close(name, got, want, scale=None, tol=CLOSE):
-    scale = want if scale is None else scale
-    got = DH.d64(got).reshape(want.shape)
-    err, big = float((got - want).abs().max()), float(scale.abs().max())
-    print(f'{name}: max error {err:.3e}, largest value {big:.3e}')
-    assert err <= tol * big, f'{name}: max error {err:.3e} against the largest value {big:.3e}'
-
-
-class Guarded:
-    """device buffers between NaN guards (16-byte aligned: the guards are 64 floats)"""
-
-    def __init__(self):
-        self.all = []
-
-    def new(self, *shape, src=None):
-        n = 1
-        for s in shape:
-            n *= s
-        raw = torch.full((n + 2 * GUARD,), NAN, device=DEV)
-        v = raw[GUARD:GUARD + n].view(*shape)
-        if src is not None:
-            v.copy_(src.reshape(shape))
-        self.all.append((raw, n))
-        return v
-
-    def check(self):
-        for raw, n in self.all:
-            assert bool(torch.isnan(raw[:GUARD]).all()) and bool(torch.isnan(raw[GUARD + n:]).all()), 'a guard was written'
-
-
-class Ops:
-    def __init__(self):
-        from diffsinger_amd import _lib
-        self.L, self.lib = _lib, _lib.load()
-        self.s = torch.cuda.current_stream().cuda_stream
-
-    def call(self, name, *args):
-        self.L.check(getattr(self.lib, name)(*args, self.s), name)
-
-    @staticmethod
-    def p(t):
-        return None if t is None else t.data_ptr()
-
+class Ops(_Ops):
     def pack_dense(self, m):
         rows, ci, kt = m.shape
         m = m.contiguous()

@@ -165,10 +165,10 @@ def test_inputs_are_validated_before_device_work():
                                (wm[:3] + [wm[3].double()] + wm[4:], bm, r'weights\[3\]'), (wm[:7] + [ws[7]], bm, r'weights\[7\]'),
                                (wm, bm[:5] + [bm[5][:3]] + bm[6:], r'biases\[5\]')):
         with pytest.raises(ValueError, match=what):
-            HD._check_s_params(xm, bad_w, bad_b, 0.1, 'disc_s_op')
+            HD._check_params(xm, bad_w, bad_b, 0.1, 'disc_s_op', HD._S_SHAPES, 'eight')
     with pytest.raises(ValueError, match='slope'):
-        HD._check_s_params(xm, wm, bm, 1.0, 'disc_s_op')
-    HD._check_s_params(xm, wm, bm[:2] + [None] + bm[3:], 0.1, 'disc_s_op')
+        HD._check_params(xm, wm, bm, 1.0, 'disc_s_op', HD._S_SHAPES, 'eight')
+    HD._check_params(xm, wm, bm[:2] + [None] + bm[3:], 0.1, 'disc_s_op', HD._S_SHAPES, 'eight')
     assert HD.launch_count() == n0
 
 
