@@ -1,12 +1,12 @@
 // fs2_cwt.hpp - the CWT pitch path of FastSpeech2 (pitch_type: cwt; C ABI in include/dsf.h, "CWT pitch"); included at the end of dsd.hip (one
-// translation unit: shares fail(), HIP_TRY, ml_sum256d of fs2_loss.hpp).
+// translation unit: shares fail(), HIP_TRY).
 //
 // What is computed, and where the reference computes it (paths relative to the reference root):
 //   k_cwt2f0        FastSpeech2.cwt2f0_norm (modules/fastspeech/fs2.py:239-245): utils/cwt.py:118-125 inverse_cwt_torch (the weighted sum of
 //                   the 10 scales, then (rec - mean) / unbiased std along the frames), :135-147 cwt2f0 (affine in the utterance's mean / std,
 //                   exp), the repeat of the last frame up to mel2ph's width, utils/pitch_utils.py:34-42 norm_f0.  One workgroup per row.
 //   k_cwt2f0_bwd    its gradient with respect to the scales, mean and std; the row statistics are the forward's (saved), everything else is
-//                   recomputed.  One workgroup per row, two block sums, one pass of stores.
+//                   recomputed.  One workgroup per row, two block sums (the tail, then both statistics at once), one pass of stores.
 //   k_cwt_loss_partial / k_cwt_loss_final / k_cwt_loss_bwd   the cwt branch of FastSpeech2Task.add_pitch_loss (tasks/tts/fs2.py:233-247):
 //                   C (l1 / l2 mean over the 10 scale channels), uv (masked BCE with logits on the last channel), f0_mean, f0_std (l1 means).
 //
@@ -14,13 +14,16 @@
 // latency, and the exp behind the affine map amplifies the rounding of its argument (|y| ~ 7: half an fp32 ulp of y is 2.4e-7 of f0).
 //
 // The reduction-order rule: a row's statistics are summed by thread i over the frames i, i + 256, ... below N (the frames that enter the
-// statistics), then by a fixed tree over the 256 threads.  N is all that order depends on - not the allocated width T, not T_out - so a
-// forward on a frame budget and a forward on the exact axis carry the same bits on the frames they share.  No atomics anywhere.
+// statistics), then by block_sum's tree over the 256 threads (block_sum.hpp).  N is all that order depends on - not the allocated width
+// T, not T_out - so a forward on a frame budget and a forward on the exact axis carry the same bits on the frames they share.  No atomics
+// anywhere.
 #pragma once
+#include "block_sum.hpp"
+#include "loss_math.hpp"
 
 namespace dsd {
 
-constexpr int kCwtBlock = 256;           // threads of every kernel here (ml_sum256d is a tree over 256)
+constexpr int kCwtBlock = 256;           // threads of every kernel here (block_sum's THREADS)
 constexpr int kCwtScales = 10;           // scales of the wavelet decomposition (utils/cwt.py: len(cwt_scales))
 constexpr int kCwtLossBlocks = 256;      // partial blocks of the loss
 
@@ -57,16 +60,15 @@ __device__ __forceinline__ int cwt_live(const CwtParams& p) {
 }
 
 __global__ __launch_bounds__(kCwtBlock) void k_cwt2f0(const CwtParams p) {
-    __shared__ double red[kCwtBlock];
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* row = p.cwt + (long long)b * p.sb;
     const int N = cwt_live(p);
     double s = 0.0;
     for (int t = tid; t < N; t += kCwtBlock) s += cwt_rec(p, row, t);
-    const double mu = ml_sum256d(s, red) / (double)N;
+    const double mu = block_sum<kCwtBlock>(s) / (double)N;
     double d = 0.0;
     for (int t = tid; t < N; t += kCwtBlock) { const double e = cwt_rec(p, row, t) - mu; d = fma(e, e, d); }
-    const double rs = 1.0 / sqrt(ml_sum256d(d, red) / (double)(N - 1));
+    const double rs = 1.0 / sqrt(block_sum_again<kCwtBlock>(d) / (double)(N - 1));
     if (tid == 0) { p.stats[2 * b] = mu; p.stats[2 * b + 1] = rs; }
     const double sd = (double)p.std[b] * (double)p.std_scale, mean = (double)p.mean[b];
     float* o = p.out + (long long)b * p.T_out;
@@ -85,7 +87,6 @@ __global__ __launch_bounds__(kCwtBlock) void k_cwt2f0(const CwtParams p) {
 // both sums over all T frames: a frame outside L has no share in mu and sigma, but its z depends on them, and that dependence lands on
 // the frames of L (d mu / d rec_j = 1 / N, d sigma / d rec_j = z_j / (N - 1) for j in L, 0 otherwise).
 __global__ __launch_bounds__(kCwtBlock) void k_cwt2f0_bwd(const CwtParams p) {
-    __shared__ double red[kCwtBlock];
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* row = p.cwt + (long long)b * p.sb;
     const float* g = p.dout + (long long)b * p.T_out;
@@ -94,18 +95,18 @@ __global__ __launch_bounds__(kCwtBlock) void k_cwt2f0_bwd(const CwtParams p) {
     const double sd = (double)p.std[b] * (double)p.std_scale, mean = (double)p.mean[b];
     double tail = 0.0;
     for (int t = p.T + tid; t < p.T_out; t += kCwtBlock) tail += (double)g[t];
-    tail = ml_sum256d(tail, red);
+    tail = block_sum<kCwtBlock>(tail);
     const double c_log = 1.0 / 0.693147180559945309417, c_std = 1.0 / (double)p.f0_std;
-    double a = 0.0, bz = 0.0;
+    double ab[2] = {0.0, 0.0};              // sum dy, sum dy z
     for (int t = tid; t < p.T; t += kCwtBlock) {
         const double z = (cwt_rec(p, row, t) - mu) * rs;
         const double gt = (double)g[t] + (t == p.T - 1 ? tail : 0.0);
         const double dy = p.norm == 2 ? gt * c_log : gt * exp(fma(z, sd, mean)) * c_std;
-        a += dy;
-        bz = fma(dy, z, bz);
+        ab[0] += dy;
+        ab[1] = fma(dy, z, ab[1]);
     }
-    a = ml_sum256d(a, red);
-    bz = ml_sum256d(bz, red);
+    block_sum_again<2, kCwtBlock>(ab);
+    const double a = ab[0], bz = ab[1];
     if (tid == 0) { p.dmean[b] = (float)a; p.dstd[b] = (float)((double)p.std_scale * bz); }
     const double ka = a / (double)N, kb = bz / (double)(N - 1);
     float* drow = p.dcwt + (long long)b * p.gsb;
@@ -139,7 +140,6 @@ struct CwtLossParams {
 };
 
 __global__ __launch_bounds__(kCwtBlock) void k_cwt_loss_partial(const CwtLossParams p) {
-    __shared__ double red[kCwtBlock];
     double a_c = 0.0, a_uv = 0.0, a_np = 0.0;
     for (long long i = blockIdx.x * (long long)kCwtBlock + threadIdx.x; i < p.n; i += (long long)gridDim.x * kCwtBlock) {
         const long long b = i / p.T, t = i - b * p.T;
@@ -153,31 +153,30 @@ __global__ __launch_bounds__(kCwtBlock) void k_cwt_loss_partial(const CwtLossPar
         if (p.use_uv) {
             const double w = p.mel2ph[i] != 0 ? 1.0 : 0.0;
             const double x = (double)pr[(long long)(p.Cp - 1) * p.sc], z = (double)p.uv[i];
-            a_uv += (fmax(x, 0.0) - x * z + log1p(exp(-fabs(x)))) * w;
+            a_uv += bce_logits(x, z) * w;
             a_np += w;
         }
     }
-    const double t0 = ml_sum256d(a_c, red), t1 = ml_sum256d(a_uv, red), t2 = ml_sum256d(a_np, red);
+    double tot[3] = {a_c, a_uv, a_np};
+    block_sum<3, kCwtBlock>(tot);
     if (threadIdx.x == 0) {
         double* o = p.partial + (size_t)blockIdx.x * 3;
-        o[0] = t0; o[1] = t1; o[2] = t2;
+        o[0] = tot[0]; o[1] = tot[1]; o[2] = tot[2];
     }
 }
 
 __global__ __launch_bounds__(kCwtBlock) void k_cwt_loss_final(const CwtLossParams p) {
-    __shared__ double red[kCwtBlock];
-    double a[3] = {0.0, 0.0, 0.0}, m = 0.0, s = 0.0;
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};       // the three partial columns, |d mean|, |d std|
     for (int i = threadIdx.x; i < p.nblk; i += kCwtBlock) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) a[k] += p.partial[(size_t)i * 3 + k];
     }
     for (int b = threadIdx.x; b < p.B; b += kCwtBlock) {
-        m += fabs((double)p.mean_pred[b] - (double)p.mean_tgt[b]);
-        s += fabs((double)p.std_pred[b] - (double)p.std_tgt[b]);
+        a[3] += fabs((double)p.mean_pred[b] - (double)p.mean_tgt[b]);
+        a[4] += fabs((double)p.std_pred[b] - (double)p.std_tgt[b]);
     }
-    const double t0 = ml_sum256d(a[0], red), t1 = ml_sum256d(a[1], red), t2 = ml_sum256d(a[2], red);
-    m = ml_sum256d(m, red);
-    s = ml_sum256d(s, red);
+    block_sum<5, kCwtBlock>(a);
+    const double t0 = a[0], t1 = a[1], t2 = a[2], m = a[3], s = a[4];
     if (threadIdx.x == 0) {
         p.out[0] = (float)(t0 / ((double)p.n * kCwtScales) * (double)p.lam_f0);
         p.out[1] = p.use_uv ? (float)(t1 / t2 * (double)p.lam_uv) : 0.f;         // an empty mask is 0 / 0 = NaN, as the reference's expression
@@ -186,8 +185,6 @@ __global__ __launch_bounds__(kCwtBlock) void k_cwt_loss_final(const CwtLossParam
         p.out[4] = (float)t2;
     }
 }
-
-__device__ __forceinline__ double cwt_sign(double d) { return d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : d); }       // torch.sign: 0 at 0, NaN stays
 
 // the gradient of the WHOLE parent tensor in one pass (scale channels, the uv logit, zeros between them) and of the two statistics
 __global__ __launch_bounds__(kCwtBlock) void k_cwt_loss_bwd(const CwtLossParams p, const float* __restrict__ stats) {
@@ -201,22 +198,20 @@ __global__ __launch_bounds__(kCwtBlock) void k_cwt_loss_bwd(const CwtLossParams 
 #pragma unroll
         for (int k = 0; k < kCwtScales; ++k) {
             const double d = (double)pr[k * p.sc] - (double)sp[k];
-            dp[k] = (float)(c_c * (p.l2 ? 2.0 * d : cwt_sign(d)));
+            dp[k] = (float)(c_c * (p.l2 ? 2.0 * d : loss_sign(d)));
         }
         for (int k = kCwtScales; k < p.Cp; ++k) dp[k] = 0.f;
         if (p.use_uv) {
             const double w = p.mel2ph[i] != 0 ? 1.0 : 0.0;
             const double x = (double)pr[(long long)(p.Cp - 1) * p.sc], z = (double)p.uv[i];
-            const double e = exp(-fabs(x));
-            const double sg = x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
-            dp[p.Cp - 1] = (float)(c_uv * (w * (sg - z)));
+            dp[p.Cp - 1] = (float)(c_uv * (w * bce_logits_grad(x, z)));
         }
     }
     if (blockIdx.x == 0) {
         const double c_m = (double)p.gout[2] * (double)p.lam_f0 / (double)p.B, c_s = (double)p.gout[3] * (double)p.lam_f0 / (double)p.B;
         for (int b = threadIdx.x; b < p.B; b += kCwtBlock) {
-            p.dmean[b] = (float)(c_m * cwt_sign((double)p.mean_pred[b] - (double)p.mean_tgt[b]));
-            p.dstd[b] = (float)(c_s * cwt_sign((double)p.std_pred[b] - (double)p.std_tgt[b]));
+            p.dmean[b] = (float)(c_m * loss_sign((double)p.mean_pred[b] - (double)p.mean_tgt[b]));
+            p.dstd[b] = (float)(c_s * loss_sign((double)p.std_pred[b] - (double)p.std_tgt[b]));
         }
     }
 }

@@ -18,6 +18,8 @@
 // streamed from L2, B = an LDS tile [channel][frame] whose taps are column offsets).
 #pragma once
 #include "dsd_kernels.hpp"
+#include "block_sum.hpp"
+#include "loss_math.hpp"
 
 namespace dsd {
 
@@ -816,7 +818,8 @@ __global__ void k_fs_p_sample(float* __restrict__ x, const float* __restrict__ e
 // (round 6: profiles/r6_42_train_glue_trace.txt - q_sample was five torch launches, the L1 loss and its backward nine):
 //   k_fs_q_sample_rows   x_noisy[b] = sqrt_alphas_cumprod[t_b] * x_start[b] + sqrt_one_minus_alphas_cumprod[t_b] * noise[b]  (:206-211; two
 //                        products and one sum, each rounded once, as the tensor ops)
-//   k_fs_l1_partial / k_fs_l1_final   mean |a - b| in a fixed order (per-thread strided sums, a tree per workgroup, one workgroup over the partials)
+//   k_fs_l1_partial / k_fs_l1_final   mean |a - b| in a fixed order (per-thread strided sums, block_sum's tree per workgroup, one workgroup over the
+//                        partials)
 //   k_fs_l1_bwd          d mean|a - b| / d b = -(sign(a - b) * (g / N)), g the DEVICE scalar arriving from autograd
 __global__ __launch_bounds__(256) void k_fs_q_sample_rows(const float* __restrict__ x0, const float* __restrict__ noise, const long long* __restrict__ t,
                                                           const float* __restrict__ tab_a, const float* __restrict__ tab_s, float* __restrict__ out, int per_row4,
@@ -835,29 +838,17 @@ __global__ __launch_bounds__(256) void k_fs_q_sample_rows(const float* __restric
     }
 }
 
-__device__ __forceinline__ float fs_block_sum256(float v, float* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] = __fadd_rn(sh[threadIdx.x], sh[threadIdx.x + o]);
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 __global__ __launch_bounds__(256) void k_fs_l1_partial(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ partial, size_t n) {
-    __shared__ float sh[256];
     float acc = 0.f;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) acc = __fadd_rn(acc, fabsf(__fsub_rn(a[i], b[i])));
-    const float tot = fs_block_sum256(acc, sh);
+    const float tot = block_sum(acc);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(256) void k_fs_l1_final(const float* __restrict__ partial, int nblk, float inv_n, float* __restrict__ out) {
-    __shared__ float sh[256];
     float acc = 0.f;
     for (int i = threadIdx.x; i < nblk; i += 256) acc = __fadd_rn(acc, partial[i]);
-    const float tot = fs_block_sum256(acc, sh);
+    const float tot = block_sum(acc);
     if (threadIdx.x == 0) out[0] = __fmul_rn(tot, inv_n);
 }
 
@@ -866,8 +857,7 @@ __global__ __launch_bounds__(256) void k_fs_l1_bwd(const float* __restrict__ a, 
     const float gn = __fmul_rn(g[0], inv_n);
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const float d = __fsub_rn(a[i], b[i]);
-        const float sg = (d > 0.f) ? 1.f : (d < 0.f) ? -1.f : d;                    // torch.sign: 0 at 0, NaN stays NaN
-        db[i] = -__fmul_rn(gn, sg);
+        db[i] = -__fmul_rn(gn, loss_sign(d));
     }
 }
 
@@ -1164,6 +1154,7 @@ __global__ void k_fs_affine(const float4* __restrict__ x, const float* __restric
     }
 }
 
+// the norm kernels' sum (wave shuffles, then the four wave totals): NOT the order of block_sum (block_sum.hpp), which the objectives use
 __device__ __forceinline__ float fs_block_sum(float v, float* red) {     // 256 threads; every thread gets the total
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

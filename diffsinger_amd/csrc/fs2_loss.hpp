@@ -16,8 +16,11 @@
 //               pdur / wdur / sdur, and (backward) their gradient wrt dur_pred.  Words are contiguous runs of phones under both segmentations,
 //               summed in phone order; the word buffer has T_txt entries, so nothing depends on the data's word count (no host sync).
 //
-// Every reduction has a fixed order (per-thread strided sums, then a tree): two evaluations are bitwise equal.  No float atomics.
+// Every reduction has a fixed order (per-thread strided sums, then block_sum's tree, block_sum.hpp; a kernel's independent sums go through
+// it in one call): two evaluations are bitwise equal.  No float atomics.
 #pragma once
+#include "block_sum.hpp"
+#include "loss_math.hpp"
 
 namespace dsd {
 
@@ -42,32 +45,6 @@ struct MelLossParams {
     int T, M, ntile, terms, weighted;    // terms: 1 L1, 2 SSIM
     float bias, lam_l1, lam_ssim;
 };
-
-__device__ __forceinline__ float ml_sum256(float v, float* sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] = __fadd_rn(sh[threadIdx.x], sh[threadIdx.x + o]);
-        __syncthreads();
-    }
-    const float r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ double ml_sum256d(double v, double* sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 // The arithmetic of the mel kernels is float64 on fp32 operands.  sigma = E - mu^2 cancels against (x + bias)^2 ~ 36 wherever target and
 // prediction are flat (padding frames): in fp32 that leaves S good to 1e-5 .. 1e-3 there, no better than any fp32 evaluation, and the
@@ -107,7 +84,6 @@ __device__ __forceinline__ MlStats ml_stats(const float* X, const float* Y, int 
 // k_mel_loss_fwd: grid (ntile, B), 256 threads; dynamic LDS: X, Y [26][M] (raw fp32 values), row flags [16].
 __global__ __launch_bounds__(256) void k_mel_loss_fwd(MelLossParams p) {
     extern __shared__ __attribute__((aligned(16))) float ml_sm[];
-    __shared__ double red[256];
     const int M = p.M, T = p.T, tid = threadIdx.x;
     const int b = blockIdx.y, t0 = blockIdx.x * kMlTile;
     constexpr int R = kMlTile + 10;
@@ -149,26 +125,24 @@ __global__ __launch_bounds__(256) void k_mel_loss_fwd(MelLossParams p) {
             a_s += S * w;
         }
     }
-    const double t_l1 = ml_sum256d(a_l1, red), t_1ms = ml_sum256d(a_1ms, red), t_s = ml_sum256d(a_s, red);
+    double tot[3] = {a_l1, a_1ms, a_s};
+    block_sum(tot);
     if (tid == 0) {
         int rows = 0;
         for (int r = 0; r < kMlTile && t0 + r < T; ++r) rows += wrow[r];
         float* o = p.partial + ((long long)b * p.ntile + blockIdx.x) * 4;
-        o[0] = (float)t_l1; o[1] = (float)t_1ms; o[2] = (float)t_s; o[3] = (float)(rows * M);
+        o[0] = (float)tot[0]; o[1] = (float)tot[1]; o[2] = (float)tot[2]; o[3] = (float)(rows * M);
     }
 }
 
 // k_mel_loss_final: one workgroup; out = [lam_l1 * L1, lam_ssim * (1 - SSIM), mean S, weight count], each a quotient by the count
 // (the reference's (l * weights).sum() / weights.sum(), then * lambda).
 __global__ __launch_bounds__(256) void k_mel_loss_final(const float* __restrict__ partial, int n, float lam_l1, float lam_ssim, float* __restrict__ out) {
-    __shared__ float red[256];
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    float tot[4] = {0.f, 0.f, 0.f, 0.f};
     for (int i = threadIdx.x; i < n; i += 256)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) a[q] = __fadd_rn(a[q], partial[(long long)i * 4 + q]);
-    float tot[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) tot[q] = ml_sum256(a[q], red);
+        for (int q = 0; q < 4; ++q) tot[q] = __fadd_rn(tot[q], partial[(long long)i * 4 + q]);
+    block_sum(tot);
     if (threadIdx.x == 0) {
         const float cnt = tot[3];
         out[0] = __fmul_rn(__fdiv_rn(tot[0], cnt), lam_l1);
@@ -258,9 +232,7 @@ __global__ __launch_bounds__(256) void k_mel_loss_bwd(MelLossParams p) {
             g = h1 + 2.0 * (xr + bias) * h11 + (yr + bias) * h12;
         }
         if ((p.terms & 1) && wrow[r + 5]) {
-            const double d = xr - yr;
-            const double sg = (d > 0.0) ? 1.0 : (d < 0.0) ? -1.0 : d;              // torch.sign: 0 at 0, NaN stays NaN
-            g += c_l1 * sg;
+            g += c_l1 * loss_sign(xr - yr);
         }
         p.dx[((long long)b * T + t) * M + m] = (float)g;
     }
@@ -288,7 +260,6 @@ constexpr int kDurRow = 8;               // floats per row in ws: pnum, pcnt, wn
 template <bool BWD>
 __global__ __launch_bounds__(256) void k_dur_loss_rows(DurLossParams p) {
     extern __shared__ __attribute__((aligned(16))) float dl_sm[];
-    __shared__ double red[256];
     __shared__ int itot[256];
     __shared__ int bad;
     const int Tt = p.Tt, T = p.T, tid = threadIdx.x, b = blockIdx.x;
@@ -386,17 +357,20 @@ __global__ __launch_bounds__(256) void k_dur_loss_rows(DurLossParams p) {
     }
     double a_sp = 0.0, a_sg = 0.0;
     for (int i = tid; i < Tt; i += 256) { a_sp += lin[i]; a_sg += gt[i]; }
-    const double S = ml_sum256d(a_sp, red), Sg = ml_sum256d(a_sg, red);
+    // one block_sum for the kernel: the forward's six sums, of which the backward needs the first two (its array is a third of the size)
+    double sums[BWD ? 2 : 6] = {a_sp, a_sg};
+    if constexpr (!BWD) { sums[2] = a_p; sums[3] = a_np; sums[4] = a_w; sums[5] = a_m; }
+    block_sum(sums);
+    const double S = sums[0], Sg = sums[1];
     const double es = log(S + 1.0) - log(Sg + 1.0);
-    if (!BWD) {
-        const double pn = ml_sum256d(a_p, red), pc = ml_sum256d(a_np, red), wn = ml_sum256d(a_w, red), wc = ml_sum256d(a_m, red);
+    if constexpr (!BWD) {
         if (tid == 0) {
             float* o = p.ws + (long long)b * kDurRow;
-            o[0] = (float)pn; o[1] = (float)pc; o[2] = (float)wn; o[3] = (float)wc; o[4] = (float)(es * es); o[5] = bad ? 1.f : 0.f;
+            o[0] = (float)sums[2]; o[1] = (float)sums[3]; o[2] = (float)sums[4]; o[3] = (float)sums[5]; o[4] = (float)(es * es); o[5] = bad ? 1.f : 0.f;
         }
         return;
     }
-    __syncthreads();                                                       // P / G of every slot written
+    // P / G of every slot are written: block_sum's barriers lie behind the loop that fills them
     const float* tot = p.ws + (long long)p.B * kDurRow;                      // pcnt, wcnt, bad (k_dur_loss_final)
     const float nanv = __int_as_float(0x7fc00000);
     const double cp = (double)p.gout[0] * (double)p.lam_p * 2.0 / (double)tot[0];
@@ -448,7 +422,8 @@ static inline size_t ml_lds_bwd(int M) {
 }
 static inline size_t dl_ints(int Tt) { return ((size_t)5 * Tt + 2) / 2 * 2; }      // cnt, raw, cs, word, D: 5 Tt + 1 words, padded to 8 bytes
 static inline size_t dl_lds(int Tt) { return dl_ints(Tt) * 4 + (size_t)4 * Tt * 8; }
-// dynamic LDS beyond 64 KiB must be allowed per kernel (M = 128: 26 / 114 KiB; T_txt = 2048: 104 KiB)
+// dynamic LDS beyond 64 KiB must be allowed per kernel (M = 128: 26 / 114 KiB; T_txt = 2048: 104 KiB); block_sum's static array comes on
+// top (k_mel_loss_fwd: 6 KiB; k_dur_loss_rows: 12 KiB forward, 4 KiB backward), the workgroup's 160 KiB bound the sum
 static int fl_lds_attr() {
     static bool done = false;
     if (!done) {

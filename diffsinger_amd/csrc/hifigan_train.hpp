@@ -15,7 +15,7 @@
 //   k_hgt_up_dgrad    transposed convolution, data gradient: dx[ci][q] = m sum_co sum_j w[ci][co][j] g[co][q u + j - p] / divide (a gather)
 //   k_hgt_rowsum_part + _reduce / _tanh_bwd / _noise_wgrad / _noise_dhar / _source_mix / _source_bwd
 //                     the bias gradients, the output tanh, the noise convolutions and the source module: plain vector-ALU kernels, float64 sums
-//                     in a fixed order (block_sum of voc_train_common.hpp).
+//                     in a fixed order (block_sum of block_sum.hpp).
 // No atomics; every sum runs in a fixed order: two calls are bitwise equal.
 #pragma once
 #include "voc_kernels.hpp"

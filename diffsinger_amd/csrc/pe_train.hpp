@@ -17,9 +17,12 @@
 //                        uv = sum(BCEWithLogits(p1, uv) np) / sum(np) lambda_uv, f0 = sum(|p0 - f0| np') / sum(np') lambda_f0 (l2: the square),
 //                        np' = np (uv == 0) under use_uv; BCE as max(x, 0) - x z + log1p(exp(-|x|)).
 //
-// fp32 throughout.  Every sum has a fixed order (per-thread strided sums, a shuffle tree per wave, the waves in order): two runs are bitwise
-// equal.  No atomics.
+// fp32 throughout.  Every sum has a fixed order: two runs are bitwise equal.  No atomics.  The norms: per-thread strided sums, a shuffle tree
+// per wave, the waves in order (fs_block_sum, fs2_kernels.hpp).  The f0 loss: per-thread strided sums, then block_sum's tree (block_sum.hpp),
+// all four sums of a kernel in one call.
 #pragma once
+#include "block_sum.hpp"
+#include "loss_math.hpp"
 
 namespace dsd {
 
@@ -252,19 +255,7 @@ struct PeF0Params {
     float lam_uv, lam_f0;
 };
 
-__device__ __forceinline__ float pe_sum256(float v, float* sh) {      // fixed-order tree over 256 threads; every thread gets the total
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 __global__ __launch_bounds__(256) void k_pe_f0_partial(const PeF0Params p) {
-    __shared__ float sh[256];
     float a_uv = 0.f, a_np = 0.f, a_f0 = 0.f, a_npv = 0.f;
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < p.n; i += (long long)gridDim.x * 256) {
         const long long b = i / p.T, t = i - b * p.T;
@@ -272,8 +263,7 @@ __global__ __launch_bounds__(256) void k_pe_f0_partial(const PeF0Params p) {
         float w = p.np[i];
         if (p.use_uv) {
             const float xl = pr[p.sc], z = p.uv[i];
-            const float bce = fmaxf(xl, 0.f) - xl * z + log1pf(expf(-fabsf(xl)));
-            a_uv += bce * w;
+            a_uv += bce_logits(xl, z) * w;
             a_np += w;
             w = w * (z == 0.f ? 1.f : 0.f);
         }
@@ -281,21 +271,22 @@ __global__ __launch_bounds__(256) void k_pe_f0_partial(const PeF0Params p) {
         a_f0 += (p.l2 ? df * df : fabsf(df)) * w;
         a_npv += w;
     }
-    const float t0 = pe_sum256(a_uv, sh), t1 = pe_sum256(a_np, sh), t2 = pe_sum256(a_f0, sh), t3 = pe_sum256(a_npv, sh);
+    float tot[4] = {a_uv, a_np, a_f0, a_npv};
+    block_sum(tot);
     if (threadIdx.x == 0) {
         float* o = p.partial + (size_t)blockIdx.x * 4;
-        o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
+        o[0] = tot[0]; o[1] = tot[1]; o[2] = tot[2]; o[3] = tot[3];
     }
 }
 
 __global__ __launch_bounds__(256) void k_pe_f0_final(const PeF0Params p) {
-    __shared__ float sh[256];
     float a[4] = {0.f, 0.f, 0.f, 0.f};
     for (int i = threadIdx.x; i < p.nblk; i += 256) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) a[k] += p.partial[(size_t)i * 4 + k];
     }
-    const float t0 = pe_sum256(a[0], sh), t1 = pe_sum256(a[1], sh), t2 = pe_sum256(a[2], sh), t3 = pe_sum256(a[3], sh);
+    block_sum(a);
+    const float t0 = a[0], t1 = a[1], t2 = a[2], t3 = a[3];
     if (threadIdx.x == 0) {
         p.out[0] = p.use_uv ? t0 / t1 * p.lam_uv : 0.f;
         p.out[1] = t2 / t3 * p.lam_f0;
@@ -316,13 +307,11 @@ __global__ __launch_bounds__(256) void k_pe_f0_bwd(const PeF0Params p, const flo
         for (int k = 1; k < p.Cp; ++k) dp[k] = 0.f;
         if (p.use_uv) {
             const float xl = pr[p.sc], z = p.uv[i];
-            const float e = expf(-fabsf(xl));
-            const float sg = xl >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-            dp[1] = c_uv * (w * (sg - z));
+            dp[1] = c_uv * (w * bce_logits_grad(xl, z));
             w = w * (z == 0.f ? 1.f : 0.f);
         }
         const float df = pr[0] - p.f0[i];
-        const float dd = p.l2 ? 2.f * df : ((df > 0.f) ? 1.f : (df < 0.f) ? -1.f : df);
+        const float dd = p.l2 ? 2.f * df : loss_sign(df);
         dp[0] = c_f0 * (w * dd);
     }
 }

@@ -20,7 +20,7 @@
 // A short row (pads < L is all the forward asks) has samples that are mirrored on both sides: the three terms are independent.
 //
 // SPECTRAL LOSS.  Forward: one pass over X and Y (float2 loads), per-thread float64 sums of (ym - xm)^2, ym^2, |ln ym - ln xm| over a
-// grid-stride walk, a fixed-order tree per workgroup (block_sum of voc_train_common.hpp), partials to a workspace; a one-workgroup second launch adds the partials in index
+// grid-stride walk, a fixed-order tree per workgroup (block_sum of block_sum.hpp), partials to a workspace; a one-workgroup second launch adds the partials in index
 // order (float64) and writes out[2] plus the two norms the backward needs.  Backward: element-wise,
 //     G = (re, im) * [ -g_sc (ym - xm) / (xm S1 S2) - g_mag sign(ln ym - ln xm) / (n P) ]        where P = re^2 + im^2 > 1e-7, else exactly 0
 // g_sc, g_mag read from device memory.  sign is taken from the clamped powers (the logarithm and the root are monotone); where ym == xm the

@@ -21,10 +21,6 @@ MAX_BINS = 128          # bins of one mel frame the SSIM kernels hold in LDS
 MAX_PHONES = 2048       # phones per utterance of the duration kernels
 
 
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _f32_rows(name, t):
     """[B, T, M] fp32 on the GPU with contiguous bins (the kernels read 4-byte elements: no alignment beyond the element's is needed)."""
     if not torch.is_tensor(t) or not t.is_cuda:
@@ -48,10 +44,8 @@ class _MelLoss(torch.autograd.Function):
         ws = torch.empty(int(lib.dsf_fs2_loss_workspace_floats(B, T, 0)), device=x.device, dtype=torch.float32)
         out = torch.empty(4, device=x.device, dtype=torch.float32)
         smap = torch.empty((B, T, M) if want_map else (0,), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.dsf_mel_loss(x.data_ptr(), x.stride(0), x.stride(1), y.data_ptr(), y.stride(0), y.stride(1), B, T, M, float(bias), int(weighted),
-                                        int(terms), float(lam_l1), float(lam_ssim), smap.data_ptr() if want_map else None, ws.data_ptr(), out.data_ptr(),
-                                        _stream(x.device)), 'dsf_mel_loss')
+        _lib.call('dsf_mel_loss', x.device, x.data_ptr(), x.stride(0), x.stride(1), y.data_ptr(), y.stride(0), y.stride(1), B, T, M, float(bias),
+                  int(weighted), int(terms), float(lam_l1), float(lam_ssim), smap.data_ptr() if want_map else None, ws.data_ptr(), out.data_ptr())
         ctx.save_for_backward(x, y, out)
         ctx.cfg = (float(bias), int(weighted), int(terms), float(lam_l1), float(lam_ssim), bool(want_map))
         return out, smap
@@ -66,10 +60,8 @@ class _MelLoss(torch.autograd.Function):
         g = g_out[:3].contiguous()
         gm = g_map.contiguous() if (want_map and g_map is not None and g_map.numel()) else None
         dx = torch.empty((B, T, M), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dsf_mel_loss_bwd(x.data_ptr(), x.stride(0), x.stride(1), y.data_ptr(), y.stride(0), y.stride(1), B, T, M, bias, weighted,
-                                                    terms, lam_l1, lam_ssim, out.data_ptr(), g.data_ptr(), gm.data_ptr() if gm is not None else None,
-                                                    dx.data_ptr(), _stream(x.device)), 'dsf_mel_loss_bwd')
+        _lib.call('dsf_mel_loss_bwd', x.device, x.data_ptr(), x.stride(0), x.stride(1), y.data_ptr(), y.stride(0), y.stride(1), B, T, M, bias, weighted,
+                  terms, lam_l1, lam_ssim, out.data_ptr(), g.data_ptr(), _lib.ptr(gm), dx.data_ptr())
         return dx, None, None, None, None, None, None, None
 
 
@@ -112,11 +104,9 @@ class _DurLoss(torch.autograd.Function):
         T = mel2ph.shape[1]
         ws = torch.empty(int(lib.dsf_fs2_loss_workspace_floats(B, Tt, 1)), device=dur_pred.device, dtype=torch.float32)
         out = torch.empty(3, device=dur_pred.device, dtype=torch.float32)
-        args = (dur_pred.data_ptr(), mel2ph.data_ptr(), tokens.data_ptr(), sil_ids.data_ptr() if sil_ids is not None else None,
-                int(sil_ids.numel()) if sil_ids is not None else 0, wdb.data_ptr() if wdb is not None else None, B, Tt, T,
-                float(lam_ph), float(lam_word), float(lam_sent))
-        with torch.cuda.device(dur_pred.device):
-            _lib.check(lib.dsf_dur_loss(*args, ws.data_ptr(), out.data_ptr(), _stream(dur_pred.device)), 'dsf_dur_loss')
+        args = (dur_pred.data_ptr(), mel2ph.data_ptr(), tokens.data_ptr(), _lib.ptr(sil_ids), int(sil_ids.numel()) if sil_ids is not None else 0,
+                _lib.ptr(wdb), B, Tt, T, float(lam_ph), float(lam_word), float(lam_sent))
+        _lib.call('dsf_dur_loss', dur_pred.device, *args, ws.data_ptr(), out.data_ptr())
         ctx.args = args
         ctx.save_for_backward(dur_pred, mel2ph, tokens, sil_ids if sil_ids is not None else ws[:0], wdb if wdb is not None else ws[:0], ws)
         return out
@@ -126,8 +116,7 @@ class _DurLoss(torch.autograd.Function):
         dur_pred, _m, _t, _s, _w, ws = ctx.saved_tensors         # kept alive: the pointers in ctx.args are theirs
         grad = torch.empty_like(dur_pred)
         g = g.contiguous()
-        with torch.cuda.device(dur_pred.device):
-            _lib.check(_lib.load().dsf_dur_loss_bwd(*ctx.args, ws.data_ptr(), g.data_ptr(), grad.data_ptr(), _stream(dur_pred.device)), 'dsf_dur_loss_bwd')
+        _lib.call('dsf_dur_loss_bwd', dur_pred.device, *ctx.args, ws.data_ptr(), g.data_ptr(), grad.data_ptr())
         return grad, None, None, None, None, None, None, None
 
 
@@ -169,11 +158,10 @@ class _CwtPitchLoss(torch.autograd.Function):
         B, T, Cp = pred.shape
         ws = torch.empty(int(lib.dsf_cwt_pitch_loss_workspace_floats()), device=pred.device, dtype=torch.float32)
         out = torch.empty(5, device=pred.device, dtype=torch.float32)
-        args = (pred.data_ptr(), pred.stride(0), pred.stride(1), pred.stride(2), spec.data_ptr(), uv.data_ptr() if use_uv else None,
-                mel2ph.data_ptr() if use_uv else None, mean_pred.data_ptr(), mean_tgt.data_ptr(), std_pred.data_ptr(), std_tgt.data_ptr(), B, T, Cp,
+        args = (pred.data_ptr(), pred.stride(0), pred.stride(1), pred.stride(2), spec.data_ptr(), _lib.ptr(uv if use_uv else None),
+                _lib.ptr(mel2ph if use_uv else None), mean_pred.data_ptr(), mean_tgt.data_ptr(), std_pred.data_ptr(), std_tgt.data_ptr(), B, T, Cp,
                 int(use_uv), int(l2), float(lam_f0), float(lam_uv))
-        with torch.cuda.device(pred.device):
-            _lib.check(lib.dsf_cwt_pitch_loss(*args, ws.data_ptr(), out.data_ptr(), _stream(pred.device)), 'dsf_cwt_pitch_loss')
+        _lib.call('dsf_cwt_pitch_loss', pred.device, *args, ws.data_ptr(), out.data_ptr())
         ctx.args = args
         ctx.save_for_backward(pred, mean_pred, std_pred, spec, uv if use_uv else spec, mel2ph if use_uv else spec, mean_tgt, std_tgt, out)
         return out
@@ -186,9 +174,7 @@ class _CwtPitchLoss(torch.autograd.Function):
         dp = torch.empty((B, T, Cp), device=pred.device, dtype=torch.float32)
         dmean = torch.empty(B, device=pred.device, dtype=torch.float32)
         dstd = torch.empty(B, device=pred.device, dtype=torch.float32)
-        with torch.cuda.device(pred.device):
-            _lib.check(_lib.load().dsf_cwt_pitch_loss_bwd(*ctx.args, out.data_ptr(), g4.data_ptr(), dp.data_ptr(), dmean.data_ptr(), dstd.data_ptr(),
-                                                          _stream(pred.device)), 'dsf_cwt_pitch_loss_bwd')
+        _lib.call('dsf_cwt_pitch_loss_bwd', pred.device, *ctx.args, out.data_ptr(), g4.data_ptr(), dp.data_ptr(), dmean.data_ptr(), dstd.data_ptr())
         return (dp, dmean, dstd) + (None,) * 9
 
 

@@ -274,10 +274,9 @@ class _F0Loss(torch.autograd.Function):
         B, T, Cp = pred.shape
         ws = torch.empty(int(lib.dsf_f0_loss_workspace_floats()), device=pred.device, dtype=torch.float32)
         out = torch.empty(4, device=pred.device, dtype=torch.float32)
-        with torch.cuda.device(pred.device):
-            _lib.check(lib.dsf_f0_loss(pred.data_ptr(), pred.stride(0), pred.stride(1), pred.stride(2), f0.data_ptr(), uv.data_ptr() if use_uv else None,
-                                       nonpadding.data_ptr(), B, T, Cp, int(use_uv), int(l2), float(lam_uv), float(lam_f0), ws.data_ptr(), out.data_ptr(),
-                                       _stream(pred.device)), 'dsf_f0_loss')
+        _lib.call('dsf_f0_loss', pred.device, pred.data_ptr(), pred.stride(0), pred.stride(1), pred.stride(2), f0.data_ptr(),
+                  _lib.ptr(uv if use_uv else None), nonpadding.data_ptr(), B, T, Cp, int(use_uv), int(l2), float(lam_uv), float(lam_f0), ws.data_ptr(),
+                  out.data_ptr())
         ctx.save_for_backward(pred, f0, uv if use_uv else f0, nonpadding, out)
         ctx.cfg = (bool(use_uv), bool(l2), float(lam_uv), float(lam_f0))
         return out
@@ -291,10 +290,9 @@ class _F0Loss(torch.autograd.Function):
         B, T, Cp = pred.shape
         g2 = g[:2].contiguous()
         dp = torch.empty((B, T, Cp), device=pred.device, dtype=torch.float32)
-        with torch.cuda.device(pred.device):
-            _lib.check(_lib.load().dsf_f0_loss_bwd(pred.data_ptr(), pred.stride(0), pred.stride(1), pred.stride(2), f0.data_ptr(),
-                                                   uv.data_ptr() if use_uv else None, nonpadding.data_ptr(), B, T, Cp, int(use_uv), int(l2), lam_uv, lam_f0,
-                                                   out.data_ptr(), g2.data_ptr(), dp.data_ptr(), _stream(pred.device)), 'dsf_f0_loss_bwd')
+        _lib.call('dsf_f0_loss_bwd', pred.device, pred.data_ptr(), pred.stride(0), pred.stride(1), pred.stride(2), f0.data_ptr(),
+                  _lib.ptr(uv if use_uv else None), nonpadding.data_ptr(), B, T, Cp, int(use_uv), int(l2), lam_uv, lam_f0, out.data_ptr(), g2.data_ptr(),
+                  dp.data_ptr())
         return dp, None, None, None, None, None, None, None
 
 
